@@ -13,9 +13,13 @@ task on one batch (+ gradient all-reduce over ranks when N>1, no optimizer).  Co
 accumulate, f32 master weights / gradients).  On 1 GPU each task's step is captured once into a hipGraph
 and replayed; dropout masks change per replay through a device-side counter.
 
-One JSON line is printed by rank 0 (see the contract in the task statement) with `roofline` (MFMA GEMM
-kernel: algorithmic FLOPs / HIP-event time per launch, measured live) and `cpu_baseline` (the CPU oracle
-= a port of the reference path, timed on the host cores of this box on a bounded sample).
+One JSON line is printed by rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (milliseconds
+per timed step) and the run's configuration.  A plain run sets up, warms up, times --steps steps and prints
+that line.  With --full it also measures per-task steps, `roofline` (MFMA GEMM kernel: algorithmic FLOPs /
+HIP-event time per launch, measured live), `cpu_baseline` (the CPU oracle = a port of the reference path,
+timed on the host cores on a bounded sample), the extra legs (fresh batch, optimizer, configs 4 / 5, large
+batches) and, at N > 1, the `dp` diagnostics.  --dump-outputs DIR writes the last timed step's loss vector
+and gradients as DIR/*.npy (float32; same arguments, same inputs).
 """
 import argparse
 import contextlib
@@ -82,6 +86,12 @@ def parse():
     ap.add_argument('--no-arena', action='store_true', help='per-parameter gradient tensors instead of the flat gradient arena')
     ap.add_argument('--cpu-batch', type=int, default=48, help='batch of the CPU-oracle timing (SURVEY 8d: the GPU workload, B = 48)')
     ap.add_argument('--layers', default='6,3,2', help='num_l_layers,num_top_layer,num_pano_layers')
+    ap.add_argument('--full', action='store_true', help='also measure everything beyond the headline: per-task steps, GEMM roofline, CPU '
+                    'baseline, fresh-batch / optimizer / config 4 / config 5 / large-batch legs, the dp diagnostics at N > 1 (the --no-* '
+                    'switches above select among them).  Off: set up, warm up, time --steps steps, print the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last timed step returned '
+                    'to its caller (its loss vector and the parameter gradients of its task; a fixed seeded sample of each large gradient) '
+                    'as DIR/<name>.npy, float32')
     return ap.parse_args()
 
 
@@ -256,8 +266,9 @@ class PhasePlan:
             yield k
 
 
-def make_steps(args, model, gb, world, wrapper, tasks=None):
-    """Returns {task: callable running one fwd+bwd(+all-reduce) step}.
+def make_steps(args, model, gb, world, wrapper, tasks=None, outputs=None):
+    """Returns {task: callable running one fwd+bwd(+all-reduce) step}.  outputs (a dict, optional) receives 'loss': {task: the
+    tensor that holds the task's loss vector after each of its steps} and 'used': {task: names of the parameters it has gradients for}.
 
     N = 1: one hipGraph per task (arena clear + forward + backward).
     N > 1: the backward pass is cut into phases (PhasePlan), each captured as its own hipGraph (one shared memory pool); the
@@ -275,6 +286,9 @@ def make_steps(args, model, gb, world, wrapper, tasks=None):
     in_graph = bool(getattr(args, 'in_graph_comm', False))
     phased = world > 1 or bool(os.environ.get('GOAT_BENCH_PHASED')) or in_graph
     plan = PhasePlan(model, int(args.layers.split(',')[0])) if phased else None
+    outputs = {} if outputs is None else outputs
+    outputs.setdefault('loss', {})
+    outputs.setdefault('used', {})
 
     def prologue(task):
         if arena[0] is not None:
@@ -288,12 +302,14 @@ def make_steps(args, model, gb, world, wrapper, tasks=None):
     def step_body(task):                        # single-graph step (N = 1, warm-up)
         prologue(task)
         loss = model(gb, task, compute_loss=True)
+        outputs['loss'][task] = loss            # (inside a capture: the graph's output, rewritten by every replay)
         hipops.backward_mean(loss)              # loss.mean().backward(): the mean for the log + a cached 1/n seed (no ones_like / div launches)
         return loss
 
     def eager_phased(task):
         prologue(task)
-        loss = model(gb, task, compute_loss=True).mean()
+        outputs['loss'][task] = model(gb, task, compute_loss=True)
+        loss = outputs['loss'][task].mean()
         last = wrapper.n_phases - 1
         for k in plan.phases(wrapper, loss):
             wrapper.reduce_gradients(task, phase=k, wait=(k == last))
@@ -308,6 +324,7 @@ def make_steps(args, model, gb, world, wrapper, tasks=None):
         for task in TASKS:                       # warm-up: builds weight shadows, index caches, kernel attrs, GEMM tuning
             step_body(task)
             wrapper.record_usage(task)           # which parameters this task produces gradients for (static)
+            outputs['used'][task] = [n for n, p in model.named_parameters() if p.grad is not None]
         if not args.no_arena:
             for p in params:
                 p.grad = None
@@ -362,7 +379,8 @@ def make_steps(args, model, gb, world, wrapper, tasks=None):
 
             def middle():
                 pd = packed.detach().requires_grad_(True)
-                cfp_losses(pd[0], pd[1], pd[2], pd[3], model.temperature, model.cfp_gather).mean().backward()
+                outputs['loss'][task] = cfp_losses(pd[0], pd[1], pd[2], pd[3], model.temperature, model.cfp_gather)
+                outputs['loss'][task].mean().backward()
                 dpacked.copy_(pd.grad)
             middle()
             gen = plan.phases(wrapper, packed, dpacked)
@@ -371,7 +389,8 @@ def make_steps(args, model, gb, world, wrapper, tasks=None):
 
             def fwd():
                 prologue(task)
-                holder['loss'] = model(gb, task, compute_loss=True).mean()
+                outputs['loss'][task] = model(gb, task, compute_loss=True)
+                holder['loss'] = outputs['loss'][task].mean()
             pool, _ = cap(fwd)
             gen = plan.phases(wrapper, holder['loss'])
         n_fwd = len(graphs)
@@ -602,14 +621,55 @@ def measure_pretrain(args, world, rank, workload, n_steps, n_warmup):
     cfg, model, batch, gb, static = build(args, rank, workload)
     wrapper = dp.GoatDataParallel(model, share_cfp_negatives=True, wire_dtype=torch.bfloat16 if args.wire == 'bf16' else None)
     wrapper.sparse_uniform_rows = True       # every rank's synthetic batch has B*L token rows (no count exchange / host sync)
-    steps = make_steps(args, model, gb, world, wrapper, tasks)
+    outputs = {}
+    steps = make_steps(args, model, gb, world, wrapper, tasks, outputs)
 
     def run(i):
         steps[tasks[i % len(tasks)]]()          # fwd + bwd (+ gradient all-reduce at N > 1)
 
     dt = timed(run, n_steps, n_warmup, world)
     return {'dt': dt, 'n_traj': synth.n_traj_steps(batch), 'cfg': cfg, 'model': model, 'batch': batch, 'gb': gb,
-            'wrapper': wrapper, 'steps': steps, 'tasks': tasks, 'run': run, 'static': static}
+            'wrapper': wrapper, 'steps': steps, 'tasks': tasks, 'run': run, 'static': static, 'outputs': outputs,
+            'last_task': tasks[(n_steps - 1) % len(tasks)] if n_steps > 0 else None}
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 16384            # elements kept of a larger gradient (the same seeded positions in every run)
+
+
+def dump_outputs(path, loss, grads):
+    """--dump-outputs: the loss vector of the last timed step and the gradients it left in `grads` ({parameter name: tensor}), as
+    float32 .npy files: `loss.npy`, `grad.<parameter name>.npy`.  A gradient of more than DUMP_SAMPLE elements is written as the
+    values at DUMP_SAMPLE sorted positions drawn from a generator seeded with 0 (flattened order), so that two builds compare
+    element for element.  -> the number of files written."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    arrays = {'loss': loss.detach().float().cpu().numpy()}
+    for name, g in grads.items():
+        flat = g.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            gen = torch.Generator().manual_seed(0)
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=gen).sort().values
+            flat = flat[idx.to(flat.device)]
+        arrays['grad.' + name] = flat.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte budget' % (total, DUMP_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    return len(arrays)
+
+
+def dump_pretrain(args, m):
+    """--dump-outputs for the pre-training workloads: the last timed step's task, its loss vector and its parameters' gradients."""
+    task = m['last_task']
+    if task is None:
+        raise RuntimeError('--dump-outputs needs at least one timed step')
+    used = set(m['outputs']['used'][task])
+    grads = {n: p.grad for n, p in m['model'].named_parameters() if n in used and p.grad is not None}
+    n = dump_outputs(args.dump_outputs, m['outputs']['loss'][task], grads)
+    print('[bench] --dump-outputs: %d arrays of the last timed step (task %s) in %s' % (n, task, args.dump_outputs), file=sys.stderr)
 
 
 def timed(run, n_steps, n_warmup, world):
@@ -942,11 +1002,13 @@ def _progress(msg):
         print('[bench +%.1fs] %s' % (_t.perf_counter() - _T0[0], msg), file=sys.stderr, flush=True)
 
 
-def config4_leg(args, rank=0, world=1):
+def config4_leg(args, rank=0, world=1, outputs=None):
     """BASELINE.json configs[3] per rank: the fine-tuning model's calls of one rollout (text once, then panorama + navigation
     per step with the [MEM] token carried: back-propagation through time) with BACL + FACL on, at the shapes of
     M/scripts/run_r2r_goat.sh (batch 12 per rank, max_instr_len 200, dictionaries 35/39/50/24, G = 60 map nodes): forward,
-    imitation loss, backward.  A trajectory-step = one panorama of one sample."""
+    imitation loss, backward.  A trajectory-step = one panorama of one sample.  The dp diagnostics, the roofline and the navigator
+    legs run under --full (and in the --leg child that --full starts).  outputs (a dict, optional) receives 'loss' (the last timed
+    episode's loss) and 'grads' ({parameter name: gradient})"""
     import vln_goat_amd
     from types import SimpleNamespace
     from vln_goat_amd import nav_model, synth, hipops
@@ -974,6 +1036,7 @@ def config4_leg(args, rank=0, world=1):
     hipops.RngState.dev = torch.zeros(1, dtype=torch.int64, device='cuda')       # per-replay dropout counter
 
     arena = [None]
+    last = {}
     from vln_goat_amd import dp
     # M/r2r/agent_base.py:100-102: vln_bert and critic both under data parallelism (rank 0's weights broadcast at construction)
     critic = nav_model.Critic(a).cuda() if hasattr(nav_model, 'Critic') else None
@@ -991,6 +1054,7 @@ def config4_leg(args, rank=0, world=1):
         #  outputs — tests/test_nav_parity_gpu.py holds both forms to the reference goldens)
         loss, _ = synth.run_nav_episode(lambda m, b: model(m, b), ep, device='cuda', hoist_text_kv=not os.environ.get('GOAT_NAV_NO_HOIST'),
                                         hoist_pano=not os.environ.get('GOAT_NAV_NO_HOIST') and not os.environ.get('GOAT_NAV_NO_PANO_HOIST'))
+        last['loss'] = loss                  # (inside a capture: the graph's output, rewritten by every replay)
         loss.backward()
 
     side = torch.cuda.Stream()
@@ -1046,8 +1110,12 @@ def config4_leg(args, rank=0, world=1):
     _progress('config4: episode captured, timing')
     n = max(6, min(args.steps, 20)) if world == 1 and args.leg else args.steps
     dt = timed(run, n, 2 if world == 1 and args.leg else args.warmup, world)
+    if outputs is not None:
+        outputs['loss'] = last['loss']
+        outputs['grads'] = {k: p.grad for k, p in model.named_parameters() if p.grad is not None}
+    full_legs = getattr(args, 'full', False) or bool(args.leg)
     dp_diag = None
-    if world > 1 or in_graph:
+    if (world > 1 or in_graph) and full_legs:
         # the diagnostics block of the pre-training workload, for the fine-tuning iteration: ranks seen, compute-only time, exchange alone
         try:
             info = [None] * world
@@ -1072,14 +1140,14 @@ def config4_leg(args, rank=0, world=1):
             dp_diag = {'error': '%s: %s' % (type(e).__name__, e)}
     _progress('config4: timed; roofline leg')
     roof = None
-    if not args.no_roofline and world == 1:
+    if not args.no_roofline and world == 1 and full_legs:
         r = gemm_roofline(args, model, None, None, cycle=episode)
         roof = {k: r[k] for k in ('bound', 'achieved', 'peak', 'unit', 'frac', 'launches_per_cycle', 'avg_launch_us',
                                   'algorithmic_gflop_per_launch', 'algorithmic_bytes_per_launch', 'gemm_ms_per_cycle', 'method')}
         roof['traffic'], roof['traffic_source'] = committed_traffic('_config4')
     _progress('config4: navigator leg')
     nav = None
-    if not args.no_graph and not os.environ.get('GOAT_BENCH_NO_NAVIGATOR') and world == 1 and not in_graph:
+    if not args.no_graph and not os.environ.get('GOAT_BENCH_NO_NAVIGATOR') and world == 1 and not in_graph and full_legs:
         try:
             nav = navigator_leg(args, model, ep, arena[0], B, T, dt / n)
         except Exception as e:      # noqa: BLE001
@@ -1684,7 +1752,11 @@ def main():
     world, rank, local = setup_dist(args)
     if args.workload == 'config4':
         # BASELINE.json configs[3]: the fine-tuning iteration, data-parallel (vln_bert + critic wrapped as M/r2r/agent_base.py:100-102)
-        r = config4_leg(args, rank, world)
+        outputs = {}
+        r = config4_leg(args, rank, world, outputs)
+        if rank == 0 and args.dump_outputs:
+            n = dump_outputs(args.dump_outputs, outputs['loss'], outputs['grads'])
+            print('[bench] --dump-outputs: %d arrays of the last timed episode in %s' % (n, args.dump_outputs), file=sys.stderr)
         if rank == 0:
             print(json.dumps({
                 'metric': 'trajectory-steps/sec fwd+bwd (GOAT fine-tune rollout, 36 views x 768, 200 tok)', 'value': r['value'], 'unit': r['unit'],
@@ -1701,15 +1773,17 @@ def main():
     per_rank = args.batch or wl['per_rank']
     m = measure_pretrain(args, world, rank, args.workload, args.steps, args.warmup)
     dt, n_traj, wrapper = m['dt'], m['n_traj'], m['wrapper']
+    if rank == 0 and args.dump_outputs:
+        dump_pretrain(args, m)
 
     # each task's step alone (same graphs, 12 replays each, all ranks take part: the steps hold collectives at N > 1)
     per_task = {}
-    for t in ([] if os.environ.get('GOAT_BENCH_NO_PER_TASK') else m['tasks']):      # (off in the counter passes: their window is the tail of the run)
+    for t in ([] if os.environ.get('GOAT_BENCH_NO_PER_TASK') or not args.full else m['tasks']):      # (off in the counter passes: their window is the tail of the run)
         n_t = 12
         dt_t = timed(lambda i, t=t: m['steps'][t](), n_t, 2, world)
         per_task[t] = round(dt_t / n_t * 1e3, 3)
     dp_diag = None
-    if world > 1 and not os.environ.get('GOAT_BENCH_NO_DP_DIAG'):
+    if world > 1 and args.full and not os.environ.get('GOAT_BENCH_NO_DP_DIAG'):
         try:
             dp_diag = dp_diagnostics(args, m, world, rank, dt)
         except Exception as e:      # noqa: BLE001  (never lose the scaling point to the diagnostics)
@@ -1736,12 +1810,14 @@ def main():
         if dp_diag is not None:
             out['dp'] = dp_diag
         headline = args.workload == 'config2' and TASKS == ('mlm', 'sap', 'cfp')
+        full = headline and args.full           # the measurements beyond the headline (--full)
         if headline:
             out['step_mfma_frac'] = round(value / world * algo * 1e9 / (MFMA_PEAK_TFLOPS[args.dtype] * 1e12), 4)
+        if full:
             out['ms_per_task_step'] = per_task
-        if world == 1 and headline and not args.no_roofline:
+        if world == 1 and full and not args.no_roofline:
             out['roofline'] = gemm_roofline(args, m['model'], m['gb'], wrapper.arena)
-        if world == 1 and headline and not args.no_extra_configs and not args.no_graph and not args.no_arena:
+        if world == 1 and full and not args.no_extra_configs and not args.no_graph and not args.no_arena:
             out['fresh_batch'] = leg('fresh_batch', lambda: fresh_batch_leg(args, m))
             if 'ms_per_step' in out['fresh_batch']:
                 out['fresh_batch_ms_per_step'] = out['fresh_batch']['ms_per_step']
@@ -1755,13 +1831,13 @@ def main():
             from vln_goat_amd import hipops
             hipops.save_tuned(os.environ['GOAT_SAVE_TUNED'])
         cfg = m['cfg']
-        if world == 1 and headline and not args.no_extra_configs and not os.environ.get('GOAT_BENCH_ONLY_FRESH'):
+        if world == 1 and full and not args.no_extra_configs and not os.environ.get('GOAT_BENCH_ONLY_FRESH'):
             m.clear()
             out['config5_reverie'] = leg_process(args, 'config5')
             out['config4_nav'] = leg_process(args, 'config4')
             if not os.environ.get('GOAT_BENCH_NO_LARGE_BATCH'):
                 out['large_batch'] = leg_process(args, 'large_batch')
-        if world == 1 and headline and not args.no_cpu_baseline:
+        if world == 1 and full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(args, cfg)
         print(json.dumps(out))
     if dist.is_initialized():

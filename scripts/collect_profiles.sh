@@ -5,12 +5,13 @@
 #   3. per-shape PMC traffic of the GEMM kernel (scripts/gemm_pmc.py) and the per-shape timing table
 # Everything lands in gpurun_out/final/; summaries are then copied into profiles/ (tracked).
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/root/repo/gpurun_out/final
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python /root/repo/bench.py --steps 30 --warmup 6 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python "$ROOT/bench.py" --steps 30 --warmup 6 --full --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -- python /root/repo/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-roofline --no-graph > $OUT/pmc_$c.log 2>&1
+  timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -- python "$ROOT/bench.py" --steps 6 --warmup 3 --full --no-cpu-baseline --no-roofline --no-graph > $OUT/pmc_$c.log 2>&1
   GEMM_PMC_ORDER=$OUT/gemm_pmc_order.json timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/gpmc_$c -- python /root/repo/scripts/gemm_pmc.py > $OUT/gpmc_$c.log 2>&1
 done
 cd /root/repo

@@ -1,9 +1,10 @@
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/root/repo/gpurun_out/pmcfinal
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -- python /root/repo/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-roofline --no-graph > $OUT/pmc_$c.log 2>&1
+  timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$c -- python "$ROOT/bench.py" --steps 6 --warmup 3 --full --no-cpu-baseline --no-roofline --no-graph > $OUT/pmc_$c.log 2>&1
 done
 cd /root/repo
 { python scripts/pmc_summary.py $OUT/pmc_FETCH_SIZE 25; python scripts/pmc_summary.py $OUT/pmc_WRITE_SIZE 25; } > $OUT/pmc_step_summary.txt

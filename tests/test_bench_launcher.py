@@ -43,7 +43,7 @@ def test_eight_rank_bench_preflight_on_one_gpu():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT', 'GOAT_BENCH_LAUNCH_ONLY'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '3', '--warmup', '1', '--batch', '4',
-                        '--layers', '2,1,1', '--no-cpu-baseline', '--no-roofline', '--no-extra-configs', '--no-autotune'],
+                        '--layers', '2,1,1', '--full', '--no-cpu-baseline', '--no-roofline', '--no-extra-configs', '--no-autotune'],
                        env=env, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

@@ -159,14 +159,14 @@ def test_feature_store_reads_a_real_hdf5_file(tmp_path):
         assert np.array_equal(h.view_block(scan, vp).numpy(), v.astype(np.float16).astype(np.float32))
 
 
-def test_h5lite_reads_files_written_by_another_hdf5_writer():
-    """files PyTables wrote (shipped with this image's conda tree as that package's test data): another writer's superblock / object header
-    versions, half / single / double precision arrays — the binding reads what libhdf5 reads."""
+def test_h5lite_reads_files_written_by_another_hdf5_writer(golden_dir):
+    """a file PyTables wrote (tests/golden/pytables_float.h5: `tables/tests/float.h5` of PyTables 3.6.1, BSD-licensed test data): another
+    writer's superblock / object header versions, half / single / double precision arrays — the binding reads what libhdf5 reads."""
     _need_hdf5()
     from vln_goat_amd import h5lite
-    path = '/opt/conda/lib/python3.9/site-packages/tables/tests/float.h5'
-    if not os.path.exists(path) or not h5lite.available():
-        pytest.skip('sample file not on this machine')
+    path = os.path.join(golden_dir, 'pytables_float.h5')
+    if not h5lite.available():
+        pytest.skip('libhdf5 not on this machine')
     with h5lite.File(path) as f:
         assert {'float16', 'float32', 'float64'} <= set(f.keys())
         want = np.add.outer(np.arange(5.0), np.arange(6.0))          # (that file's arrays hold i + j)
