@@ -8,7 +8,7 @@
 The reference reads its pre-extracted CLIP / ViT view features and object features with h5py; this image ships no h5py, but it does ship
 the C library itself (/opt/conda/lib/libhdf5.so.103, HDF5 1.10.6).  The format work — superblock, B-trees, heaps, chunking, filters, type
 conversion — is libhdf5's; this module only marshals handles and buffers.  `features.FeatureStore.from_hdf5` and
-`rollout.ObjectStore.from_hdf5` prefer h5py when it is importable and fall back to this module.
+`navsim.ObjectStore.from_hdf5` prefer h5py when it is importable and fall back to this module.
 
 Supported: datasets of integer / float element types of any rank (read whole, converted by the library to the native type of the same
 class and size), attributes of those types, fixed- and variable-length string attributes / datasets (-> numpy object arrays of str, as

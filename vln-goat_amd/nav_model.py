@@ -5,7 +5,7 @@ FACL (front-door: attention over K-means CFP features) — SURVEY.md §8a rows a
 
 `VLNBert.forward(mode, batch)` with mode in {language, panorama, navigation, instr_zdict_update,
 extract_cfp_features}; return types and parameter names/shapes as the reference (M/models/vilmodel_GOAT.py:847-927).
-R2R / RxR branch (REVERIE/SOON object tokens: not built yet).
+R2R / RxR branch and the REVERIE / SOON branch (object tokens behind the views of every panorama, object-grounding logits).
 """
 import collections
 

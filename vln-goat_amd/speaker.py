@@ -1,7 +1,7 @@
 """The "transpeaker" — the transformer speaker of the fine-tuning loop's back-translation augmentation (last item):
 `Transpeaker` of M/models/transpeaker_model.py:232-257 (M = /root/reference/map_nav_src) on the HIP kernels, with the reference's
 `state_dict` keys, plus the two uses of it in M/r2r/transpeaker.py: the teacher-forced loss (:209-246) and greedy / sampled decoding
-(`infer_batch`, :248-318), and the feature walk along the ground-truth path (`from_shortest_path`, :158-199) on rollout.GraphSim.
+(`infer_batch`, :248-318), and the feature walk along the ground-truth path (`from_shortest_path`, :158-199) on navsim.GraphSim.
 
 Reference behaviour kept (file:line in M/models/transpeaker_model.py):
   * MultiHeadAttention (:91-119): bias-free projections, heads of size `aemb` (64: the head size of goat_attn_*), boolean masks filled
@@ -249,12 +249,12 @@ def path_features(sim, store, episodes, angle_size=128):
     36 view features + their relative angle features (`speaker_feature` of the observation, M/r2r/env.py:362-364) and the feature of
     the view in which the next viewpoint is seen (zeros at the stop step).  -> (img_feats [B, T, 36, F], can_feats [B, T, F]
     float32 on the store's device, lengths [B])."""
-    from . import rollout
+    from . import navsim
     obs = sim.reset(episodes)
     B = len(obs)
     D = store.table.shape[1]
     F = D + angle_size
-    table = rollout.view_angle_feature_table(angle_size)
+    table = navsim.view_angle_feature_table(angle_size)
     ended = np.zeros(B, bool)
     lengths = np.zeros(B, np.int64)
     rows, angs, crow, cang = [], [], [], []
@@ -275,7 +275,7 @@ def path_features(sim, store, episodes, angle_size=128):
             else:
                 c = next(c for c in ob['candidate'] if c['viewpointId'] == nxt)
                 cr[i] = ob['feature_row'] * 36 + c['pointId']
-                ca[i] = rollout.angle_feature(c['heading'], c['elevation'], angle_size)
+                ca[i] = navsim.angle_feature(c['heading'], c['elevation'], angle_size)
                 moves.append((nxt, c['pointId']))
         rows.append(r)
         angs.append(a)

@@ -56,7 +56,7 @@ class graph:
         # (torch emits that warning ONCE per process: after a first, possibly harmless occurrence this net no longer catches anything.  Making it
         #  fire every time was tried in round 6 and is too strict: a parameter whose AccumulateGrad node was created on one CAPTURING stream and
         #  receives its gradient from another capturing stream (graphs of several tasks kept alive side by side) warns too, and that case is
-        #  correct.  rollout.SinglePassSampledEpisode checks for live earlier graphs in its eager warm-up instead.)
+        #  correct.  sampled.SinglePassSampledEpisode checks for live earlier graphs in its eager warm-up instead.)
         try:
             from . import dp
             dp.quiesce_if_needed()      # eager RCCL collectives issued so far are retired before the stream enters capture mode (dp.quiesce_collectives)
@@ -124,7 +124,7 @@ class Branch:
         if Branch.mode != 'always' and not torch.cuda.is_current_stream_capturing():
             return self
         if not torch.is_grad_enabled():
-            # forward-only capture (rollout.SampledEpisode): nothing is saved for a backward pass, so a tensor made on the caller's stream
+            # forward-only capture (sampled.SampledEpisode): nothing is saved for a backward pass, so a tensor made on the caller's stream
             # and read by the branch is released as soon as Python drops it and its block is handed to the caller's next allocation while
             # the branch may still read it (the allocator orders reuse per allocating stream) — measured: action probabilities that
             # change from replay to replay.  The inference graphs are small and host-paced; they run on one stream.

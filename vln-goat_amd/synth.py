@@ -465,7 +465,7 @@ def run_nav_episode(model, ep, device='cpu', use_bacl=True, use_facl=True, to_fl
 
 # ------------------------------------------------------------------------------------------------ rollout cases
 def rollout_episodes(scan, rs, B=3, max_steps=5, starts=None):
-    """B episodes on a rollout.ScanGraph: ground-truth path = shortest path from a start viewpoint to a distant one (cut to
+    """B episodes on a navsim.ScanGraph: ground-truth path = shortest path from a start viewpoint to a distant one (cut to
     max_steps viewpoints), random start heading, random instruction ids between <s> (0) and </s> (2)."""
     eps = []
     n = len(scan.vpids)
@@ -496,10 +496,10 @@ def reverie_episodes(scan, objects, rs, B=3, max_steps=5, starts=None):
 
 def make_reverie_rollout_case(seed=23, n_nodes=22, B=3, max_steps=5, scan_seed=12, max_objects=5):
     """make_rollout_case with objects on the viewpoints and a target object per episode (REVERIE): -> scan, features, episodes,
-    dictionaries, rollout.ObjectStore (float32 table on the host; `.to(device)` before use)."""
-    from . import rollout
+    dictionaries, navsim.ObjectStore (float32 table on the host; `.to(device)` before use)."""
+    from . import navsim
     scan, feats, _, dicts = make_rollout_case(seed, n_nodes, B, max_steps, scan_seed)
-    objects = rollout.ObjectStore.synthetic([scan], D=768, max_objects=max_objects, seed=seed + 1, dtype=torch.float32, p_empty=0.2)
+    objects = navsim.ObjectStore.synthetic([scan], D=768, max_objects=max_objects, seed=seed + 1, dtype=torch.float32, p_empty=0.2)
     eps = reverie_episodes(scan, objects, np.random.RandomState(seed + 2), B, max_steps)
     return scan, feats, eps, dicts, objects
 
@@ -508,9 +508,9 @@ def make_rollout_case(seed=17, n_nodes=24, B=3, max_steps=5, scan_seed=9):
     """scan, float32 features [n_vp, 36, 768], episodes and the BACL / FACL dictionaries (in the reference's on-disk shapes:
     [K, 768] features, [K] probabilities) of the end-to-end rollout golden (tests/golden/rollout_episode.npz).  numpy
     RandomState: bit-stable across machines."""
-    from . import rollout
+    from . import navsim
     rs = np.random.RandomState(seed)
-    scan = rollout.ScanGraph.synthetic('scanB', n=n_nodes, seed=scan_seed, degree=3)
+    scan = navsim.ScanGraph.synthetic('scanB', n=n_nodes, seed=scan_seed, degree=3)
     feats = rs.standard_normal((len(scan.vpids), 36, 768)).astype(np.float32)
     eps = rollout_episodes(scan, rs, B, max_steps)
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
@@ -527,7 +527,7 @@ def make_rollout_case(seed=17, n_nodes=24, B=3, max_steps=5, scan_seed=9):
 
 
 def rollout_extras(dicts, B, device):
-    """the confounder dictionaries as the per-mode extra inputs of rollout.NavRollout.run: what M/r2r/agent.py:53-58,138-140,
+    """the confounder dictionaries as the per-mode extra inputs of NavRollout.run (rollout.py): what M/r2r/agent.py:53-58,138-140,
     491-511 does with z_dicts / z_front_dict (repeat over the batch)."""
     dev = torch.device(device)
     rep = lambda t, w: t.to(dev).reshape(1, -1, w).repeat(B, 1, 1)
