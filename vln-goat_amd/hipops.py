@@ -52,118 +52,18 @@ def manual_seed(seed=None):
     RngState.counter = 0
 
 
-# ----------------------------------------------------------------------------- weight shadows
-# Cached operand copies of the float32 master weights (bf16 casts, K-/row-padded and concatenated images).  A captured
-# hipGraph has their ADDRESSES baked in, so a stale copy is always rebuilt INTO ITS OWN STORAGE, never replaced by a new
-# tensor: graphs captured before an optimizer step read the updated weights after it (optim.FusedAdamW refreshes most copies
-# inside its update kernel and the rest through `refresh_shadows`).
-def _store_shadow(cache, key, ver, w):
-    ent = cache.get(key)
-    if ent is not None and ent[1].shape == w.shape and ent[1].dtype == w.dtype and ent[1].device == w.device:
-        ent[1].copy_(w)
-        cache[key] = (ver, ent[1])
-        return ent[1]
-    cache[key] = (ver, w)
-    return w
-
-
-def _build_shadow(param, dtype, transposed, pad_k):
-    with torch.no_grad():
-        w = param.detach()
-        if pad_k:
-            w = torch.nn.functional.pad(w, (0, pad_k))
-        if transposed:
-            w = w.t()
-        return w.to(dtype).contiguous()
-
-
-def _shadow(param, dtype, transposed=False, pad_k=0):
-    """dtype-cast (and optionally transposed / K-padded) copy of a float32 master weight, cached."""
-    key = (dtype, transposed, pad_k)
-    cache = param.__dict__.setdefault('_goat_shadow', {})
-    ent = cache.get(key)
-    ver = param._version
-    if ent is not None and ent[0] == ver and ent[1].device == param.device:
-        return ent[1]
-    return _store_shadow(cache, key, ver, _build_shadow(param, dtype, transposed, pad_k))
-
-
-def _build_cat(params, dtype, transposed):
-    with torch.no_grad():
-        w = torch.cat([p.detach() for p in params], 0)
-        if transposed:
-            w = w.t()
-        return w.to(dtype).contiguous()
-
-
-def _shadow_cat(params, dtype, transposed=False):
-    """Row-concatenation of several [N_i,K] weights (fused QKV / KV projection), cached on the first."""
-    key = ('cat', dtype, transposed, tuple(id(p) for p in params))
-    cache = params[0].__dict__.setdefault('_goat_shadow', {})
-    ver = tuple(p._version for p in params)
-    ent = cache.get(key)
-    if ent is not None and ent[0] == ver and ent[1].device == params[0].device:
-        return ent[1]
-    return _store_shadow(cache, key, ver, _build_cat(params, dtype, transposed))
-
-
-def _build_catb(biases):
-    with torch.no_grad():
-        return torch.cat([x.detach().float() for x in biases], 0).contiguous()
-
-
-def _cat_bias(biases):
-    key = ('catb', tuple(id(b) for b in biases))
-    cache = biases[0].__dict__.setdefault('_goat_shadow', {})
-    ver = tuple(b._version for b in biases)
-    ent = cache.get(key)
-    if ent is not None and ent[0] == ver and ent[1].device == biases[0].device:
-        return ent[1]
-    return _store_shadow(cache, key, ver, _build_catb(biases))
-
-
-def _build_rows_padded(param, dtype, rows):
-    with torch.no_grad():
-        w = torch.zeros((rows, param.shape[1]), dtype=dtype, device=param.device)
-        w[:param.shape[0]] = param.detach().to(dtype)
-        return w
-
-
-def refresh_shadows(param, by_id, done=()):
-    """Rebuild, in place, every cached copy hanging off `param` whose storage address is not in `done` (the copies an update
-    kernel has already refreshed).  For an optimizer that writes the masters through raw pointers (no version bump).
-    by_id: {id(parameter): parameter} of every parameter that may be a member of a concatenated copy."""
-    cache = param.__dict__.get('_goat_shadow')
-    if not cache:
-        return 0
-    n = 0
-    for key, (ver, t) in list(cache.items()):
-        if t.data_ptr() in done:
-            continue
-        if key[0] == 'cat':
-            members = [by_id.get(i) for i in key[3]]
-            if any(m is None for m in members):
-                del cache[key]          # a member is gone: nothing can read this copy any more
-                continue
-            t.copy_(_build_cat(members, key[1], key[2]))
-        elif key[0] == 'catb':
-            members = [by_id.get(i) for i in key[1]]
-            if any(m is None for m in members):
-                del cache[key]
-                continue
-            t.copy_(_build_catb(members))
-        elif key[0] == 'rowpad':
-            t.copy_(_build_rows_padded(param, key[1], key[2]))
-        elif key[0] == 'bpad':
-            t.copy_(_build_bias_padded(param, key[1]))
-        else:
-            t.copy_(_build_shadow(param, key[0], key[1], key[2]))
-        n += 1
-    return n
+# ----------------------------------------------------------------------------- weight shadows: shadows.py
+from .shadows import _bias_padded, _cat_bias, _shadow, _shadow_cat, _shadow_rows_padded, _store_shadow, refresh_shadows      # noqa: E402,F401
 
 
 # ----------------------------------------------------------------------------- raw kernels
 # (PROFILE — bench.py's per-launch HIP-event timing — lives in tuning.py beside the autotuner state; `hipops.PROFILE` is an alias)
+def _profile_start():
+    """(tuning.PROFILE is a list) -> (start, stop) timing events of one launch, `start` recorded: the head of its tuning.PROFILE entry
+    (start, stop, flops, shape key, (C symbol, its arguments for a replay, the tensors they point into))."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0, e1
 
 
 def gemm_nt(a, b, out, bias=None, epi=EPI_NONE, aux=None, split_k=1):
@@ -171,22 +71,19 @@ def gemm_nt(a, b, out, bias=None, epi=EPI_NONE, aux=None, split_k=1):
     M, K = a.shape
     N = b.shape[0]
     assert b.shape[1] == K and out.shape[0] == M and out.shape[1] == N
-    if tuning.PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ev = _profile_start() if tuning.PROFILE is not None else None
     st = _lib.lib().goat_gemm_nt(_stream(), _dt(a), _dt(out), _ptr(a), a.stride(0), _ptr(b), b.stride(0),
                                  _ptr(out), out.stride(0), M, N, K,
                                  _ptr(bias) if bias is not None else None, epi,
                                  _ptr(aux) if aux is not None else None,
                                  aux.stride(0) if aux is not None else 0, split_k)
     _lib.check(st, 'goat_gemm_nt(M=%d,N=%d,K=%d)' % (M, N, K))
-    if tuning.PROFILE is not None:
-        e1.record()
-        tuning.PROFILE.append((e0, e1, 2.0 * M * N * K, (M, N, K, epi, split_k, str(a.dtype)),
-                        ('goat_gemm_nt', (_dt(a), _dt(out), _ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(out), out.stride(0),
-                                          M, N, K, _ptr(bias) if bias is not None else None, epi,
-                                          _ptr(aux) if aux is not None else None, aux.stride(0) if aux is not None else 0,
-                                          split_k), (a, b, out, bias, aux))))
+    if ev is not None:
+        ev[1].record()
+        cargs = (_dt(a), _dt(out), _ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(out), out.stride(0), M, N, K,
+                 _ptr(bias) if bias is not None else None, epi, _ptr(aux) if aux is not None else None,
+                 aux.stride(0) if aux is not None else 0, split_k)
+        tuning.PROFILE.append(ev + (2.0 * M * N * K, (M, N, K, epi, split_k, str(a.dtype)), ('goat_gemm_nt', cargs, (a, b, out, bias, aux))))
     return out
 
 
@@ -293,18 +190,16 @@ def gemm(a, b, out, ta=False, tb=False, bias=None, epi=EPI_NONE, aux=None, split
     if accumulate and split_k == 1:
         assert epi == EPI_NONE and out.dtype == torch.float32 and bias is None
         epi = EPI_ACCUM
-    if tuning.PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    ev = _profile_start() if tuning.PROFILE is not None else None
     _launch_gemm_bf16(a, b, out, ta, tb, M, N, Kc, bias, epi, aux, split_k, bm, nstage, colsum_out)
-    if tuning.PROFILE is not None:
-        e1.record()
+    if ev is not None:
+        ev[1].record()
         cargs = (int(ta), int(tb), _dt(out), _ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(out),
                  out.stride(0), M, N, Kc, _ptr(bias) if bias is not None else None, epi,
                  _ptr(aux) if aux is not None else None, aux.stride(0) if aux is not None else 0,
                  split_k, bm, nstage, _ptr(colsum_out) if colsum_out is not None else None)
-        tuning.PROFILE.append((e0, e1, 2.0 * M * N * Kc, (M, N, Kc, epi, split_k, 'v2 t%d%d %s %s' % (ta, tb, tile_name(bm), stage_name(nstage))),
-                        ('goat_gemm_bf16', cargs, (a, b, out, bias, aux, colsum_out))))
+        tuning.PROFILE.append(ev + (2.0 * M * N * Kc, (M, N, Kc, epi, split_k, 'v2 t%d%d %s %s' % (ta, tb, tile_name(bm), stage_name(nstage))),
+                                    ('goat_gemm_bf16', cargs, (a, b, out, bias, aux, colsum_out))))
     return out
 
 
@@ -314,65 +209,16 @@ from .streams import Branch, graph, note_parallel_branch, _RETAINED_GRAPHS      
 from .wgrad_queue import LnReduceQueue, WgradQueue                                   # noqa: E402,F401
 
 
-def _sink(param, keep_queued=False):
-    """Gradient-arena slice bound to `param` (dp.GradArena.attach), or None.  When it is bound — i.e. still the
-    object behind param.grad — backward passes accumulate the parameter's gradient straight into it and return
-    None to autograd (no temporary, no zero-fill, no `grad += dW` kernel).  Setting param.grad = None (or to any
-    other tensor) silently restores the ordinary autograd path.
-    keep_queued: the caller is about to queue ANOTHER weight-gradient problem for this slice on this stream and the two may be merged
-    (WgradQueue.mergeable): a queued write of the same stream then stays queued."""
-    if param is None:
-        return None
-    if WgradQueue.pending_ids and id(param) in WgradQueue.pending_ids:
-        if not (keep_queued and WgradQueue.pending_ids[id(param)] == torch.cuda.current_stream().cuda_stream):
-            WgradQueue.flush_param(id(param))      # a queued write of this slice must land before anything else touches it
-    s = param.__dict__.get('_goat_sink')
-    return s if (s is not None and param.grad is s) else None
+# gradient sinks (arena slices the backward passes write straight into): the protocol is gradsink.py
+from .gradsink import ARENA_EPOCH, _first_touch, _prep_fallback, _sink, _sink_cat, small_sinks      # noqa: E402,F401
 
 
-def _sink_cat(params, keep_queued=False):
-    """One [sum(rows), ...] view over the arena slices of several parameters if they are adjacent in the arena
-    (query/key/value weights of a block), else None."""
-    sinks = [_sink(p, keep_queued) for p in params]
-    if any(t is None for t in sinks):
-        return None
-    for a, b in zip(sinks, sinks[1:]):
-        if a.data_ptr() + a.numel() * a.element_size() != b.data_ptr() or a.shape[1:] != b.shape[1:]:
-            return None
-    s0 = sinks[0]
-    return torch.as_strided(s0, (sum(t.shape[0] for t in sinks),) + tuple(s0.shape[1:]), s0.stride())
-
-
-ARENA_EPOCH = [0]       # bumped by dp.GradArena.zero(): a sink's first use in a step overwrites / clears its slice
-
-
-def _first_touch(*params):
-    """True if none of `params` has been written through its sink yet in this step (marks them written).
-    Small parameters (`_goat_prezero`: biases, LayerNorm, ...) are cleared by GradArena.zero() at the start of the step:
-    they never count as a first touch — writers just accumulate.  Mixed states among the others (some written, some
-    not) cannot be served by one kernel launch: the unwritten slices are cleared here and the call is an accumulation."""
-    cur = ARENA_EPOCH[0]
-    params = [p for p in params if not p.__dict__.get('_goat_prezero')]
-    if not params:
-        return False
-    seen = [p.__dict__.get('_goat_epoch') == cur for p in params]
-    for p, was in zip(params, seen):
-        p.__dict__['_goat_epoch'] = cur
-        if not was and any(seen):
-            p.__dict__['_goat_sink'].zero_()
-    return not any(seen)
-
-
-def _prep_fallback(*params):
-    """A Function is about to return ordinary gradients for `params` (autograd will add them into .grad): if a
-    .grad is an arena slice nobody has written yet in this step it still holds the previous step's values."""
-    for p in params:
-        t = _sink(p)
-        if t is not None and _first_touch(p):
-            t.zero_()
-
-
-def _wgrad_impl(dy, x, want_bias, w_sink=None, b_sink=None, first=False, b_first=False, defer_ids=None):
+def wgrad(dy, x, want_bias, w_sink=None, b_sink=None, first=False, b_first=False, defer_ids=None):
+    """dW[N,K] (f32) = dy[M,N]^T @ x[M,K] ; db[N] (f32) = colsum(dy), fused into the same kernel.
+    One zero-fill covers both outputs (split-K partial tiles and the bias sums are accumulated atomically).
+    With sinks (gradient-arena slices) the results are accumulated in place — deferred into a grouped launch when
+    possible (WgradQueue) — and (None, None) is returned.  (Measured and dropped: running each weight-gradient GEMM on a
+    second stream next to the dgrad chain was slower, 9.9 vs 9.3 ms per step.)"""
     M, N = dy.shape
     K = x.shape[1]
     # default (bm 64, split) from scripts/wgrad_sweep.py; the autotuner may pick another split (output is zero-filled)
@@ -416,16 +262,37 @@ def _wgrad_impl(dy, x, want_bias, w_sink=None, b_sink=None, first=False, b_first
     return dw, db
 
 
-def wgrad(dy, x, want_bias, w_sink=None, b_sink=None, first=False, b_first=False, defer_ids=None):
-    """dW[N,K] (f32) = dy[M,N]^T @ x[M,K] ; db[N] (f32) = colsum(dy), fused into the same kernel.
-    One zero-fill covers both outputs (split-K partial tiles and the bias sums are accumulated atomically).
-    With sinks (gradient-arena slices) the results are accumulated in place — deferred into a grouped launch when
-    possible (WgradQueue) — and (None, None) is returned.  (Measured and dropped: running each weight-gradient GEMM on a
-    second stream next to the dgrad chain was slower, 9.9 vs 9.3 ms per step.)"""
-    return _wgrad_impl(dy, x, want_bias, w_sink, b_sink, first, b_first, defer_ids)
+def linear_wgrad(dy, x, weights, biases, want_bias=True):
+    """wgrad() of a Linear's weight — or of a run of weights whose outputs are concatenated in dy — through the gradient-sink protocol
+    (gradsink.py), in its fixed order: look the sinks up (a queued write of a slice lands first unless the two problems may be merged),
+    stamp first touches, clear the stale slices of whatever falls back to autograd, launch or queue.  A bias is only sunk when its
+    weight is.  -> (dw, db) as wgrad returns them: None for what went into a sink.  biases: one per weight (None: no bias)."""
+    keep = WgradQueue.mergeable(dy.shape[0], dy.shape[1], x.shape[1])      # small (BPTT-step) problems of one weight are merged into one
+    if len(weights) == 1:
+        w_sink = _sink(weights[0], keep)
+        b_sink = _sink(biases[0], keep) if w_sink is not None else None
+    else:
+        w_sink = _sink_cat(weights, keep)
+        b_sink = _sink_cat(biases, keep) if w_sink is not None else None
+    if w_sink is None:
+        _prep_fallback(*weights, *biases)
+        return wgrad(dy, x, want_bias)
+    first = _first_touch(*weights)
+    b_first = b_sink is not None and _first_touch(*biases)
+    if b_sink is None:
+        _prep_fallback(*biases)
+    return wgrad(dy, x, want_bias, w_sink, b_sink, first, b_first, [id(t) for t in weights] + [id(t) for t in biases if t is not None])
 
 
 # ----------------------------------------------------------------------------- Linear
+def _rows(x, dtype=None):
+    """x[..., H] as a contiguous [rows, H] matrix, cast to `dtype` (if given) before it is made contiguous."""
+    x2 = x.reshape(-1, x.shape[-1])
+    if dtype is not None and x2.dtype != dtype:
+        x2 = x2.to(dtype)
+    return x2 if x2.is_contiguous() else x2.contiguous()
+
+
 def _pad_k(x, e):
     K = x.shape[1]
     pad = (-K) % e
@@ -476,11 +343,7 @@ class _LinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         x2, aux = ctx.saved_tensors
         weight = ctx.weight
-        dy2 = dy.reshape(-1, dy.shape[-1])
-        if dy2.dtype != x2.dtype:
-            dy2 = dy2.to(x2.dtype)
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
+        dy2 = _rows(dy, x2.dtype)
         if ctx.act not in (None, 'none'):
             dy2 = act_bwd(dy2, aux, ctx.act)
         dx = dw = db = None
@@ -495,34 +358,24 @@ class _LinearFn(torch.autograd.Function):
             # short-input Linear (7- / 14-wide position features, K padded to a 16-byte chunk for the GEMM): one kernel adds the
             # weight and bias gradients straight into the arena slices (otherwise: padded GEMM into a temporary, slice copy, grad += dW)
             K = x2.shape[1] - ctx.pad
-            w_sink = _sink(weight)
-            b_sink = _sink(ctx.bias) if (ctx.has_bias and w_sink is not None) else None
-            if w_sink is not None and (b_sink is not None or not ctx.has_bias):
-                if _first_touch(weight):
-                    w_sink.zero_()
-                if b_sink is not None and _first_touch(ctx.bias):
-                    b_sink.zero_()
-                dwt, dbt = w_sink, b_sink
+            sinks = small_sinks((weight, ctx.bias) if ctx.has_bias else (weight,))
+            if sinks is not None:
+                dwt, dbt = sinks[0], (sinks[1] if ctx.has_bias else None)
             else:
-                _prep_fallback(weight, *([ctx.bias] if ctx.has_bias else []))
                 dwt = torch.zeros(weight.shape, dtype=torch.float32, device=dy2.device)
                 dbt = torch.zeros(weight.shape[0], dtype=torch.float32, device=dy2.device) if ctx.has_bias else None
             st = _lib.lib().goat_wgrad_smallk(_stream(), _dt(dy2), _ptr(dy2), dy2.stride(0), _ptr(x2), x2.stride(0), dy2.shape[0],
                                               dy2.shape[1], K, _ptr(dwt), dwt.stride(0), _ptr(dbt) if dbt is not None else None)
             _lib.check(st, 'goat_wgrad_smallk')
-            if dwt is not w_sink:
+            if sinks is None:
                 dw, db = dwt, dbt
         elif ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            keep = WgradQueue.mergeable(dy2.shape[0], dy2.shape[1], x2.shape[1])      # small (BPTT-step) problems of one weight are merged into one
-            w_sink = None if ctx.pad else _sink(weight, keep)
-            b_sink = _sink(ctx.bias, keep) if w_sink is not None else None
-            first = w_sink is not None and _first_touch(weight)
-            b_first = b_sink is not None and _first_touch(ctx.bias)
-            _prep_fallback(*(([] if w_sink is not None else [weight]) + ([] if b_sink is not None else [ctx.bias])))
-            ids = [id(weight)] + ([id(ctx.bias)] if b_sink is not None else [])
-            dw, db = wgrad(dy2, x2, ctx.has_bias, w_sink, b_sink, first, b_first, ids if w_sink is not None else None)
-            if ctx.pad:
+            if ctx.pad:           # K-padded input: dW comes out padded — through a temporary, never into the sink
+                _prep_fallback(weight, ctx.bias)
+                dw, db = wgrad(dy2, x2, ctx.has_bias)
                 dw = dw[:, :x2.shape[1] - ctx.pad].contiguous()
+            else:
+                dw, db = linear_wgrad(dy2, x2, (weight,), (ctx.bias,), ctx.has_bias)
         return dx, dw, db, None, None
 
 
@@ -533,9 +386,7 @@ class _RowDotFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias):
         _need_gpu(x)
-        x2 = x.reshape(-1, x.shape[-1])
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows(x)
         M, H = x2.shape
         y = torch.empty(M, dtype=x2.dtype, device=x2.device)
         st = _lib.lib().goat_rowdot_fwd(_stream(), _dt(x2), _ptr(x2), _ptr(weight), _ptr(bias) if bias is not None else None, _ptr(y), M, H)
@@ -558,16 +409,10 @@ class _RowDotFn(torch.autograd.Function):
         need_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
         dw = db = dwt = dbt = None
         if need_w:
-            w_sink = _sink(weight)
-            b_sink = _sink(bias) if (bias is not None and w_sink is not None) else None
-            if w_sink is not None and (b_sink is not None or bias is None):
-                if _first_touch(weight):
-                    w_sink.zero_()
-                if b_sink is not None and _first_touch(bias):
-                    b_sink.zero_()
-                dwt, dbt = w_sink, b_sink
+            sinks = small_sinks((weight, bias) if bias is not None else (weight,))
+            if sinks is not None:
+                dwt, dbt = sinks[0], (sinks[1] if bias is not None else None)
             else:
-                _prep_fallback(weight, *([bias] if bias is not None else []))
                 buf = torch.zeros(H + 1, dtype=torch.float32, device=x2.device)
                 dwt, dbt = buf[:H], (buf[H:] if bias is not None else None)
                 dw, db = dwt.view(weight.shape), (dbt.view(bias.shape) if bias is not None else None)
@@ -607,9 +452,7 @@ class _FfnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, act, p):
         _need_gpu(x)
-        x2 = x.reshape(-1, x.shape[-1])
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows(x)
         W1 = _shadow(w1, x2.dtype)
         W2 = _shadow(w2, x2.dtype)
         M, F_ = x2.shape[0], W1.shape[0]
@@ -631,9 +474,7 @@ class _FfnFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x2, u, h = ctx.saved_tensors
-        dy2 = dy.reshape(-1, dy.shape[-1])
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
+        dy2 = _rows(dy)
         W2 = _shadow(ctx.w2, x2.dtype)  # [H, F]
         du = torch.empty_like(u)
         if ctx.p > 0:
@@ -641,23 +482,11 @@ class _FfnFn(torch.autograd.Function):
             du = act_bwd(du, u, ctx.act, ctx.p, ctx.rng)
         else:
             gemm(dy2, W2, du, tb=True, epi=_ACT_DEPI[ctx.act], aux=u)
-        k2 = WgradQueue.mergeable(dy2.shape[0], dy2.shape[1], h.shape[1])
-        s2 = _sink(ctx.w2, k2)
-        sb2 = _sink(ctx.b2, k2) if s2 is not None else None
-        f2 = s2 is not None and _first_touch(ctx.w2)
-        bf2 = sb2 is not None and _first_touch(ctx.b2)
-        _prep_fallback(*(([] if s2 is not None else [ctx.w2]) + ([] if sb2 is not None else [ctx.b2])))
-        dw2, db2 = wgrad(dy2, h, True, s2, sb2, f2, bf2, [id(ctx.w2), id(ctx.b2)] if s2 is not None else None)
+        dw2, db2 = linear_wgrad(dy2, h, (ctx.w2,), (ctx.b2,))
         W1 = _shadow(ctx.w1, x2.dtype)  # [F, H]
         dx = torch.empty_like(x2)
         gemm(du, W1, dx, tb=True)
-        k1 = WgradQueue.mergeable(du.shape[0], du.shape[1], x2.shape[1])
-        s1 = _sink(ctx.w1, k1)
-        sb1 = _sink(ctx.b1, k1) if s1 is not None else None
-        f1 = s1 is not None and _first_touch(ctx.w1)
-        bf1 = sb1 is not None and _first_touch(ctx.b1)
-        _prep_fallback(*(([] if s1 is not None else [ctx.w1]) + ([] if sb1 is not None else [ctx.b1])))
-        dw1, db1 = wgrad(du, x2, True, s1, sb1, f1, bf1, [id(ctx.w1), id(ctx.b1)] if s1 is not None else None)
+        dw1, db1 = linear_wgrad(du, x2, (ctx.w1,), (ctx.b1,))
         return dx.view(ctx.xshape), dw1, db1, dw2, db2, None, None
 
 
@@ -666,34 +495,6 @@ def ffn(x, w1, b1, w2, b2, act='gelu', p=0.0):
 
 
 # ----------------------------------------------------------------------------- tied decoder + cross-entropy (MLM)
-def _build_bias_padded(bias, n):
-    with torch.no_grad():
-        b = torch.zeros(n, dtype=torch.float32, device=bias.device)
-        b[:bias.numel()] = bias.detach().float()
-        return b
-
-
-def _bias_padded(bias, n):
-    """float32 [n] copy of a bias with zeros behind it (the 64-padded vocabulary of the MLM decoder), cached like _shadow: built
-    once, refreshed in place — not a fill + a copy in every step."""
-    key = ('bpad', n)
-    cache = bias.__dict__.setdefault('_goat_shadow', {})
-    ent = cache.get(key)
-    if ent is not None and ent[0] == bias._version and ent[1].device == bias.device:
-        return ent[1]
-    return _store_shadow(cache, key, bias._version, _build_bias_padded(bias, n))
-
-
-def _shadow_rows_padded(param, dtype, rows):
-    """[rows, K] copy of a [N, K] weight (N <= rows, extra rows zero), cached like _shadow."""
-    key = ('rowpad', dtype, rows)
-    cache = param.__dict__.setdefault('_goat_shadow', {})
-    ent = cache.get(key)
-    if ent is not None and ent[0] == param._version and ent[1].device == param.device:
-        return ent[1]
-    return _store_shadow(cache, key, param._version, _build_rows_padded(param, dtype, rows))
-
-
 class _DecoderCeFn(torch.autograd.Function):
     """loss[m] = CE(h[m] @ W^T + b, target[m])  — BertLMPredictionHead.decoder + F.cross_entropy
     (P/model/Bert_backbone.py:826-829, P/model/pretrain_goat.py:210-216).  The vocabulary dimension is padded
@@ -704,8 +505,7 @@ class _DecoderCeFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, weight, bias, targets):
         _need_gpu(h)
-        h2 = h.reshape(-1, h.shape[-1])
-        h2 = h2 if h2.is_contiguous() else h2.contiguous()
+        h2 = _rows(h)
         M, K = h2.shape
         N = weight.shape[0]
         Np = (N + 63) // 64 * 64
@@ -741,6 +541,7 @@ class _DecoderCeFn(torch.autograd.Function):
         else:
             dh = torch.empty_like(h2)
             gemm(dl, _shadow_rows_padded(weight, h2.dtype, Nl), dh, tb=True)
+        # (not through linear_wgrad: whether the weight is sunk decides which columns of dl are the problem, before anything else happens)
         w_sink = _sink(weight)
         if w_sink is not None:      # the tied word-embedding table: accumulate next to the embedding scatter-add
             b_sink = _sink(ctx.bias)
@@ -769,9 +570,7 @@ class _MultiLinearFn(torch.autograd.Function):
         n = len(wb) // 2
         ws, bs = wb[:n], wb[n:]
         _need_gpu(x)
-        x2 = x.reshape(-1, x.shape[-1])
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows(x)
         W = _shadow_cat(ws, x2.dtype)
         b = _cat_bias(bs)
         out = torch.empty((x2.shape[0], W.shape[0]), dtype=x2.dtype, device=x2.device)
@@ -784,23 +583,14 @@ class _MultiLinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         (x2,) = ctx.saved_tensors
         ws = ctx.ws
-        dy2 = dy.reshape(-1, dy.shape[-1])
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
+        dy2 = _rows(dy)
         dx = None
         if ctx.needs_input_grad[0]:
             W = _shadow_cat(ws, x2.dtype)
             dx = torch.empty_like(x2)
             gemm(dy2, W, dx, tb=True)
             dx = dx.view(ctx.xshape)
-        keep = WgradQueue.mergeable(dy2.shape[0], dy2.shape[1], x2.shape[1])
-        w_sink = _sink_cat(ws, keep)
-        b_sink = _sink_cat(ctx.bs, keep) if w_sink is not None else None
-        first = w_sink is not None and _first_touch(*ws)
-        b_first = b_sink is not None and _first_touch(*ctx.bs)
-        _prep_fallback(*(([] if w_sink is not None else list(ws)) + ([] if b_sink is not None else list(ctx.bs))))
-        ids = [id(t) for t in ws] + [id(t) for t in ctx.bs]
-        dw, db = wgrad(dy2, x2, True, w_sink, b_sink, first, b_first, ids if w_sink is not None else None)
+        dw, db = linear_wgrad(dy2, x2, ws, ctx.bs)
         sizes = [w.shape[0] for w in ws]
         none = (None,) * len(ws)
         return (dx,) + (tuple(torch.split(dw, sizes, 0)) if dw is not None else none) \
@@ -836,9 +626,7 @@ class _LinearBankFn(torch.autograd.Function):
         m = len(wb) // 2
         ws, bs = wb[:m], wb[m:]
         _need_gpu(x)
-        x2 = x.reshape(-1, x.shape[-1])
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows(x)
         W = _shadow_cat(ws, x2.dtype)
         b = _cat_bias(bs)
         out = torch.empty((x2.shape[0], W.shape[0]), dtype=x2.dtype, device=x2.device)
@@ -876,14 +664,7 @@ class _LinearBankFn(torch.autograd.Function):
         for i in range(n):
             wi, bi = ws[i * per:(i + 1) * per], ctx.bs[i * per:(i + 1) * per]
             dyi = dy2[:, i * width:(i + 1) * width]
-            keep = WgradQueue.mergeable(dyi.shape[0], dyi.shape[1], x2.shape[1])
-            w_sink = _sink_cat(wi, keep)
-            b_sink = _sink_cat(bi, keep) if w_sink is not None else None
-            first = w_sink is not None and _first_touch(*wi)
-            b_first = b_sink is not None and _first_touch(*bi)
-            _prep_fallback(*(([] if w_sink is not None else list(wi)) + ([] if b_sink is not None else list(bi))))
-            ids = [id(t) for t in wi] + [id(t) for t in bi]
-            dw, db = wgrad(dyi, x2, True, w_sink, b_sink, first, b_first, ids if w_sink is not None else None)
+            dw, db = linear_wgrad(dyi, x2, wi, bi)
             sizes = [w.shape[0] for w in wi]
             dws += list(torch.split(dw, sizes, 0)) if dw is not None else [None] * per
             dbs += list(torch.split(db, sizes, 0)) if db is not None else [None] * per
@@ -929,14 +710,8 @@ class _LnFn(torch.autograd.Function):
             raise ValueError('z_out returns the pre-norm sum residual + dropout(x): it needs a residual')
         ctx.fork_in, ctx.z_out = fork_in, z_out
         H = x.shape[-1]
-        x2 = x.reshape(-1, H)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        r2 = None
-        if residual is not None:
-            r2 = residual.reshape(-1, H)
-            if not r2.is_contiguous():
-                r2 = r2.contiguous()
+        x2 = _rows(x)
+        r2 = _rows(residual) if residual is not None else None
         M = x2.shape[0]
         y = torch.empty_like(x2)
         need_z = (r2 is not None) or p > 0
@@ -952,8 +727,7 @@ class _LnFn(torch.autograd.Function):
             seed, dev = s2, d2
         pa = None
         if post_add is not None:             # y = dropout_out(LayerNorm(z) + post_add)
-            pa = post_add.reshape(-1, H).to(x2.dtype)
-            pa = pa if pa.is_contiguous() else pa.contiguous()
+            pa = _rows(post_add, x2.dtype)
         ctx.has_post = pa is not None
         st = _lib.lib().goat_ln_fwd_do(_stream(), _dt(x2), _ptr(x2), _ptr(r2) if r2 is not None else None,
                                        _ptr(gamma), _ptr(beta), eps, p, seed, off, dev,
@@ -988,21 +762,11 @@ class _LnFn(torch.autograd.Function):
                 dy, dyb = dyb, None
         p, seed, off, dev = ctx.rng
         H = z.shape[-1]
-        dy2 = dy.reshape(-1, H)
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
+        dy2 = _rows(dy)
         if dskip is not None:
-            dskip = dskip.reshape(-1, H)
-            if dskip.dtype != z.dtype:
-                dskip = dskip.to(z.dtype)
-            if not dskip.is_contiguous():
-                dskip = dskip.contiguous()
+            dskip = _rows(dskip, z.dtype)
         if dyb is not None:
-            dyb = dyb.reshape(-1, H)
-            if dyb.dtype != dy2.dtype:
-                dyb = dyb.to(dy2.dtype)
-            if not dyb.is_contiguous():
-                dyb = dyb.contiguous()
+            dyb = _rows(dyb, dy2.dtype)
         M = z.shape[0]
         L = _lib.lib()
         dx = torch.empty_like(z)
@@ -1333,15 +1097,11 @@ class _PanoFusionFn(torch.autograd.Function):
         N, V, H = x.shape
         df = df if df.is_contiguous() else df.contiguous()
         dx = torch.empty_like(x)
-        sa, sb = _sink(ctx.params[0]), _sink(ctx.params[1])
-        sunk = PANO_SINK and sa is not None and sb is not None and sa.is_contiguous()
+        sinks = small_sinks(ctx.params)      # (bound slices are cleared on first touch whether the kernel then adds into them or not)
+        sunk = PANO_SINK and sinks is not None and sinks[0].is_contiguous()
         if sunk:                 # arena slices: the kernel's atomics add straight into them
-            for prm, snk in zip(ctx.params, (sa, sb)):
-                if _first_touch(prm):
-                    snk.zero_()
-            da, da0 = sa.view(-1), sb.view(-1)
+            da, da0 = sinks[0].view(-1), sinks[1].view(-1)
         else:
-            _prep_fallback(*ctx.params)
             da = torch.zeros(H, dtype=torch.float32, device=x.device)
             da0 = torch.zeros(1, dtype=torch.float32, device=x.device)
         st = _lib.lib().goat_pano_fusion_bwd(_stream(), _dt(x), _ptr(x), _ptr(av), _ptr(a_b), _ptr(wsave), _ptr(df),
@@ -1571,10 +1331,8 @@ class _DoorGateFn(torch.autograd.Function):
     def forward(ctx, aug, ori, wa, ba, wo, bo):
         _need_gpu(aug)
         H = aug.shape[-1]
-        a2 = aug.reshape(-1, H)
-        o2 = ori.reshape(-1, H).to(a2.dtype)
-        a2 = a2 if a2.is_contiguous() else a2.contiguous()
-        o2 = o2 if o2.is_contiguous() else o2.contiguous()
+        a2 = _rows(aug)
+        o2 = _rows(ori, a2.dtype)
         wav, wov = wa.detach().reshape(-1).contiguous(), wo.detach().reshape(-1).contiguous()
         rows = a2.shape[0]
         out = torch.empty_like(a2)
@@ -1592,22 +1350,17 @@ class _DoorGateFn(torch.autograd.Function):
         a2, o2, wav, wov, gate = ctx.saved_tensors
         ashape, oshape, odtype, washape, woshape = ctx.shapes
         rows, H = a2.shape
-        d2 = dout.reshape(rows, H).to(a2.dtype)
-        d2 = d2 if d2.is_contiguous() else d2.contiguous()
+        d2 = _rows(dout, a2.dtype)
         daug, dori = torch.empty_like(a2), torch.empty_like(a2)
-        sinks = [_sink(p_) for p_ in ctx.params]
-        if all(t is not None for t in sinks):
+        sinks = small_sinks(ctx.params)
+        if sinks is not None:
             # gradient arena: the four gate parameters are small (cleared by GradArena.zero at the start of the step, never a first touch) —
             # the kernel's atomics add straight into their slices; a gate used in every step of an episode would otherwise cost a zero fill,
             # a clone and four AccumulateGrad adds per use
-            for p_ in ctx.params:
-                if _first_touch(p_):
-                    _sink(p_).zero_()
             st = _lib.lib().goat_door_gate_bwd(_stream(), _dt(a2), _ptr(a2), _ptr(o2), _ptr(wav), _ptr(wov), _ptr(gate), _ptr(d2),
                                                _ptr(daug), _ptr(dori), _ptr(sinks[0]), _ptr(sinks[2]), _ptr(sinks[1]), rows, H, _ptr(sinks[3]))
             _lib.check(st, 'goat_door_gate_bwd')
             return daug.view(ashape), dori.view(oshape).to(odtype), None, None, None, None
-        _prep_fallback(*ctx.params)
         buf = torch.zeros(2 * H + 1, dtype=torch.float32, device=a2.device)
         st = _lib.lib().goat_door_gate_bwd(_stream(), _dt(a2), _ptr(a2), _ptr(o2), _ptr(wav), _ptr(wov), _ptr(gate), _ptr(d2),
                                            _ptr(daug), _ptr(dori), _ptr(buf), _ptr(buf, H), _ptr(buf, 2 * H), rows, H, None)
@@ -1642,8 +1395,7 @@ class _DictWsumFn(torch.autograd.Function):
         zf, pf = ctx.saved_tensors
         zdtype, pshape, pdtype = ctx.meta
         B, K, H = zf.shape
-        d2 = dout.reshape(B, H)
-        d2 = d2 if d2.is_contiguous() else d2.contiguous()
+        d2 = _rows(dout)
         dz = torch.empty_like(zf) if ctx.needs_input_grad[0] else None
         dp = torch.empty_like(pf) if ctx.needs_input_grad[1] else None
         st = _lib.lib().goat_dict_wsum_bwd(_stream(), _dt(d2), _ptr(d2), _ptr(zf), _ptr(pf), _ptr(dz) if dz is not None else None,

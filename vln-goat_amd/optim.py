@@ -16,6 +16,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .shadows import BPAD, CAT, CATB, PLAIN, ROWPAD, key_kind, member_ids
 
 NO_DECAY = ('bias', 'LayerNorm.bias', 'LayerNorm.weight')      # P/optim/misc.py:13
 CHUNK = 65536
@@ -84,7 +85,8 @@ class FusedAdamW:
         {'s0', 's1': bf16 pointers in the parameter's element order, 'cols', 'ld0': s0 is a row-padded image, 'f32': float32
         pointer} and done = the storage addresses of the copies that are COMPLETELY covered by the slots handed out (a
         concatenated copy only when each of its members got one).  Everything else is rebuilt in place after the kernel by
-        hipops.refresh_shadows — a cached copy is never dropped: a captured hipGraph may read it at its address."""
+        hipops.refresh_shadows — a cached copy is never dropped: a captured hipGraph may read it at its address.
+        (Key layouts: the table at the top of shadows.py.)"""
         by_id = {id(p): p for p in plist}
         slots = {id(p): {'bf16': [], 'pad': None, 'f32': None} for p in plist}
         whole = []            # (tensor, [(param id, kind, pointer)]) per cached copy
@@ -95,29 +97,30 @@ class FusedAdamW:
             for k, (ver, t) in cache.items():
                 if not t.is_contiguous():
                     continue
-                if k[0] == 'cat':
-                    if k[1] != torch.bfloat16 or k[2] or any(i not in by_id for i in k[3]):
+                kd = key_kind(k)
+                if kd == CAT:
+                    if k[1] != torch.bfloat16 or k[2] or any(i not in by_id for i in member_ids(k)):
                         continue
                     row, members = 0, []
-                    for i in k[3]:
+                    for i in member_ids(k):
                         members.append((i, 'bf16', t.data_ptr() + row * t.shape[1] * 2))
                         row += by_id[i].shape[0]
                     whole.append((t, members))
-                elif k[0] == 'catb':
-                    if t.dtype != torch.float32 or any(i not in by_id for i in k[1]):
+                elif kd == CATB:
+                    if t.dtype != torch.float32 or any(i not in by_id for i in member_ids(k)):
                         continue
                     off, members = 0, []
-                    for i in k[1]:
+                    for i in member_ids(k):
                         members.append((i, 'f32', t.data_ptr() + off * 4))
                         off += by_id[i].numel()
                     whole.append((t, members))
-                elif k[0] == 'rowpad':
+                elif kd == ROWPAD:
                     if t.dtype == torch.bfloat16 and t.shape[1:] == p.shape[1:] and t.shape[0] >= p.shape[0]:
                         whole.append((t, [(id(p), 'bf16', t.data_ptr())]))
-                elif k[0] == 'bpad':          # zero-padded float32 image of a bias: the leading numel(p) floats are the bias
+                elif kd == BPAD:          # zero-padded float32 image of a bias: the leading numel(p) floats are the bias
                     if t.dtype == torch.float32 and t.numel() >= p.numel():
                         whole.append((t, [(id(p), 'f32', t.data_ptr())]))
-                elif k[0] == torch.bfloat16 and k[1] is False and t.dtype == torch.bfloat16:
+                elif kd == PLAIN and k[0] == torch.bfloat16 and k[1] is False and t.dtype == torch.bfloat16:
                     if k[2] == 0:
                         whole.append((t, [(id(p), 'bf16', t.data_ptr())]))
                     elif p.dim() == 2:
