@@ -785,6 +785,70 @@ def test_gemm_bf16_persistent_matches_one_workgroup_per_tile(ops, bm, tb):
         assert torch.equal(run(0x202, EPI_MUL_DGELU, aux0), run(0x602, EPI_MUL_DGELU, aux0))
 
 
+@pytest.mark.parametrize('width,off', [(399, 1), (400, 0)])
+def test_gemm_bf16_shared_epilogue_ragged_columns_on_every_loop(ops, width, off):
+    """The result stores the three main loops share (csrc/gemm_epilogue.hpp), where N = 392 of the tests above never takes them: N = 397 ends
+    in a partial 16-byte chunk, and C / aux are column slices of a wider buffer.  (399, 1): odd row stride, pointer off the 16-byte grid —
+    every chunk of C and aux, and every read of the saved pre-activation, goes element by element.  (400, 0): 16-byte stores with the
+    element-wise tail.  One tile per loop (lockstep 4-wave, lockstep 8-wave, ping-pong, persistent); bias, GELU / ReLU (+ saved
+    pre-activation), x GELU' / x ReLU', float32 + bias.  Columns outside the slice keep their sentinel; persistent == ping-pong bitwise."""
+    from vln_goat_amd._lib import EPI_GELU, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_NONE, EPI_RELU
+    M, N, Kc = 300, 397, 192
+    g = torch.Generator().manual_seed(397)
+    a = torch.randn(M, Kc, generator=g).to(DEV, torch.bfloat16)
+    b = (torch.randn(N, Kc, generator=g) * 0.1).to(DEV, torch.bfloat16)
+    bias = torch.randn(N, generator=g).to(DEV)
+    ref = a.float() @ b.float().T
+    SENTINEL = 7.0
+
+    def sliced(dtype=torch.bfloat16):
+        wide = torch.full((M, width), SENTINEL, device=DEV, dtype=dtype)
+        view = wide[:, off:off + N]
+        assert view.stride(0) == width and view.data_ptr() == wide.data_ptr() + off * wide.element_size()
+        return view, wide
+
+    def run(bm, ns, epi=EPI_NONE, aux=None, bias_=None, dtype=torch.bfloat16):
+        out, wide = sliced(dtype)
+        ops._launch_gemm_bf16(a, b, out, False, False, M, N, Kc, bias_, epi, aux, 1, bm, ns, None)
+        return out, wide
+
+    def untouched(wide, what):
+        outside = torch.cat([wide[:, :off], wide[:, off + N:]], 1)
+        assert bool((outside == SENTINEL).all()), '%s: columns outside the slice were written' % what
+
+    results = {}
+    for bm, ns in ((128, 2), (128 | 256 << 16, 2), (128, 0x202), (128, 0x602)):
+        what = 'tile %#x nstage %#x ' % (bm, ns)
+        got = []
+        out, wide = run(bm, ns, bias_=bias)
+        _close(out, ref + bias, torch.bfloat16, what + 'plain')
+        untouched(wide, what + 'plain')
+        got.append(out)
+        for act, dact, fn in ((EPI_GELU, EPI_MUL_DGELU, torch.nn.functional.gelu), (EPI_RELU, EPI_MUL_DRELU, torch.relu)):
+            aux, aux_wide = sliced()
+            out, wide = run(bm, ns, act, aux, bias)
+            _close(aux, ref + bias, torch.bfloat16, what + 'saved pre-activation')
+            _close(out, fn(ref + bias), torch.bfloat16, what + 'activation')
+            untouched(wide, what + 'activation')
+            untouched(aux_wide, what + 'saved pre-activation')
+            uu = aux.float().requires_grad_(True)
+            fn(uu).sum().backward()
+            dout, wide = run(bm, ns, dact, aux)
+            _close(dout, ref * uu.grad, torch.bfloat16, what + "x act'")
+            untouched(wide, what + "x act'")
+            got += [out, aux, dout]
+        if ns & 0x400:          # the persistent loop has bf16 results only: goat_gemm_bf16 refuses float32 there (GOAT_E_ARG = -1) and writes nothing
+            with pytest.raises(RuntimeError, match='status -1'):
+                run(bm, ns, bias_=bias, dtype=torch.float32)
+        else:
+            out32, wide = run(bm, ns, bias_=bias, dtype=torch.float32)
+            _close(out32, ref + bias, torch.bfloat16, what + 'f32 result with bias')
+            untouched(wide, what + 'f32')
+        results[ns] = got
+    for x, y in zip(results[0x202], results[0x602]):
+        assert torch.equal(x, y), 'persistent and ping-pong results differ'
+
+
 def test_wgrad_grouped(ops):
     """goat_wgrad_grouped: several dW_i = dY_i^T · X_i problems of different shapes (ragged rows, row-strided dY) in one
     launch, with bias column sums; both tile heights."""

@@ -18,13 +18,22 @@
 // BM = 32*MI*WM rows, BN = 32*NI*WN columns, BK = 64.  Why the big tiles: scripts/l2_lds_bw.hip measures what a CU can pull
 // from its XCD's L2 into LDS at 50-58 B/clk when the data is L2-resident and 18-40 B/clk when it comes from the Infinity
 // Cache; at the MFMA peak a 128x128 tile consumes 64 B/clk, 256x128 48, 192x256 37, 256x256 32 (profiles/round2_l2_lds_bw.txt).
+//
+// The result stores are gemm_epilogue.hpp's (shared with the ping-pong loops).  This loop's choices: every wave stages through slice
+// `wave` of the drained ring; block row 0 of the saved pre-activation of the x act' epilogues is requested before the drain barrier and two
+// block rows are kept in flight where the accumulators leave room (none otherwise); float32 stores follow GOAT_G2_STORE.
+// (A deliberate change of schedule, the only one of the move into the shared header: this loop used to hold the same two buffers but request
+// block row i + 1 at the top of block row i; now row i + 2 goes out as soon as row i has been handed to LDS, and the wait for row i + 1 no
+// longer covers the result stores of row i.  Same registers, same results; 3840 x 3072 x 768 x GELU' 27.2 -> 26.9 us on 192 x 256, 29.9 -> 29.1 on
+// 128 x 128 x 8 waves, profiles/gemm_epilogue_fold_ab.txt.)
 #pragma once
 #include <algorithm>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
-#include "common.hpp"
+#include "gemm_epilogue.hpp"
 
 namespace goat_g2 {
 
@@ -66,18 +75,6 @@ typedef Cfg<2, 4, 4, 2> T256x256;   // 256 x 256, 8 waves
 typedef Cfg<2, 3, 3, 2> T192x192;   // 192 x 192, SIX waves (3840 x 2304: 20 x 12 = 240 tiles — one round on 256 CUs; 256 x 192 gives 180)
 typedef Cfg<1, 4, 3, 1> T96;        //  96 x 128, 4 waves  (M = 3840 = 40 x 96: 240 tiles at N = 768 — one round on 256 CUs, against 180 tiles of 128 x 128)
 
-struct G2Args {
-  const void* A; const void* B; void* C; const float* bias; void* aux;
-  int64_t lda, ldb, ldc, ldaux;
-  int M, N, Kc;
-  int tiles_m, tiles_n;
-  int k_tiles_per_split;
-  uint32_t a_bytes, b_bytes;  // buffer sizes for the bounds check
-  float* colsum;              // TA only: colsum[m] += sum_k A[k,m]  (bias gradient fused into wgrad)
-  int accum;                  // f32 output, no split: C += A·B (read-modify-write) instead of C = A·B
-  int group_m;                // tile order: column-major inside groups of group_m tile rows (L2-sized 2-D blocks per XCD)
-};
-
 typedef __attribute__((address_space(3))) void lds_void;
 
 __device__ __forceinline__ uint4 lds_read_b128(uint32_t addr) {
@@ -97,26 +94,6 @@ template <int N_> __device__ __forceinline__ void wait_lgkm() {
 template <int N_> __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory");
 }
-// 16-byte result store (inline asm ends in `s_nop 1`: the compiler does not know the statement is a >64-bit VMEM store and would
-// otherwise overwrite the data registers inside the store-data hazard window — seen as isolated wrong elements).
-// GOAT_G2_STORE: 0 plain, 1 nt (non-temporal), 2 sc1 (write-through: the line leaves the XCD's L2 right
-// away instead of in the write-back burst at the end of the kernel, MI355X_MICROARCH.md "publish-large")
-#ifndef GOAT_G2_STORE
-#define GOAT_G2_STORE 1       // measured: 3840x3072x768 25.9 (plain) -> 21.5 us (nt), 8640x3072x768 64.1 -> 47.7 us
-#endif
-typedef uint32_t g2_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store16(void* dst, const uint4& v) {
-#if GOAT_G2_STORE == 1
-  const g2_u32x4 q = {v.x, v.y, v.z, v.w};
-  asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" ::"v"(dst), "v"(q) : "memory");
-#elif GOAT_G2_STORE == 2
-  const g2_u32x4 q = {v.x, v.y, v.z, v.w};
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(q) : "memory");
-#else
-  *reinterpret_cast<uint4*>(dst) = v;
-#endif
-}
-
 // Per-operand tile geometry.  ROWS x RB bytes, lane-linear LDS image, swizzled source.
 template <bool T, int BMN>
 struct Tile {
@@ -163,40 +140,6 @@ __device__ __forceinline__ uint32_t frag_addr_t(uint32_t tile_base, int kr, int 
 __device__ __forceinline__ int xcd_chunk_position(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
-
-// Saved-activation block rows fetched ahead of the epilogue (two of them in flight); empty in instantiations without the prefetch.
-template <bool ON, int CHUNKS> struct AuxRows {
-  uint4 v[2][CHUNKS];
-  __device__ __forceinline__ uint4* row(int i) { return v[i]; }
-};
-template <int CHUNKS> struct AuxRows<false, CHUNKS> {
-  __device__ __forceinline__ uint4* row(int) { return nullptr; }
-};
-
-// One 32-row block row of a wave's patch of the saved pre-activation (bf16, G2Args::aux): CHUNKS 16-byte pieces per lane, rows
-// and columns past the problem read as zero.
-template <int CHUNKS, int CPR>
-__device__ __forceinline__ void load_aux_rows(const G2Args& p, int row_w, int col_w, int lane, uint4* dst) {
-  constexpr int EPC = 8;
-  const bf16_t* auxp = reinterpret_cast<const bf16_t*>(p.aux);
-  const bool vec = auxp != nullptr && (p.ldaux % EPC) == 0 && ((reinterpret_cast<uintptr_t>(auxp) & 15) == 0);
-#pragma unroll
-  for (int c = 0; c < CHUNKS; ++c) {
-    const int idx = c * 64 + lane, r = idx / CPR, cc = idx % CPR;
-    const int row = row_w + r, col = col_w + cc * EPC;
-    uint4 raw = {0u, 0u, 0u, 0u};
-    if (row < p.M) {
-      if (col + EPC <= p.N && vec) {
-        raw = *reinterpret_cast<const uint4*>(auxp + (int64_t)row * p.ldaux + col);
-      } else {
-        bf16_t* rv = reinterpret_cast<bf16_t*>(&raw);
-        for (int e = 0; e < EPC; ++e)
-          if (col + e < p.N) rv[e] = auxp[(int64_t)row * p.ldaux + col + e];
-      }
-    }
-    dst[c] = raw;
-  }
 }
 
 template <class CF, bool TA, bool TB, int NSTAGE>
@@ -293,7 +236,8 @@ __device__ __forceinline__ void gemm2_tile(const G2Args& p, int bid, int split) 
                                                offb[(j_) >= IPWA ? (j_) - IPWA : 0], (uint32_t)(t_) * kb, 0, 0); \
   } while (0)
 
-  f32x16 acc[MI][NI];
+  AccTile<MI, NI> accs;
+  f32x16 (&acc)[MI][NI] = accs.t;
 #pragma unroll
   for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -488,19 +432,14 @@ __device__ __forceinline__ void gemm2_tile(const G2Args& p, int bid, int split) 
   }
 #endif
 #undef GOAT_MMA
-  // activation-derivative epilogues (FFN dgrad): the saved pre-activation of this wave's patch is fetched one 32-row block row
-  // AHEAD of its use — block row 0 here, behind the last MFMAs and across the pipeline drain, block row i + 1 while block row i is
-  // being combined and stored — so that only the first of the MI dependent HBM round trips is (partly) exposed.  Round 2 loaded each
-  // block row right where it was needed: 399 TFLOP/s on 3840 x 3072 x 768 against 548 for the same shape without the multiply.
-  constexpr bool DACT_ = !SPLITK && sizeof(OutT) == 2 && (EPI == GOAT_EPI_MUL_DGELU || EPI == GOAT_EPI_MUL_DRELU);
-  constexpr int EPC_ = 8, CPR_ = WCOLS / EPC_, CHUNKS_ = 32 * CPR_ / 64;
-  // (only in instantiations whose accumulators leave room for two block rows of it, and through a free function: the first version
-  //  of this — a [&] lambda defined here in every instantiation — cost the 256 x 256 transposed-operand kernels 5 to 162 spilled
-  //  registers although they never call it, and the grouped weight-gradient launch of that tile went from 297 to 446 us;
-  //  profiles/round3_gemm_spill_check.txt)
-  constexpr bool PF_ = DACT_ && (MI * NI * 16 + 2 * CHUNKS_ * 4 <= 128);
-  AuxRows<PF_, CHUNKS_> auxr;
-  if constexpr (PF_) load_aux_rows<CHUNKS_, CPR_>(p, m0 + wm * WROWS, n0 + wn * WCOLS, lane, auxr.row(0));
+  // x act' epilogues (FFN dgrad): block row 0 of the saved pre-activation is requested HERE, behind the last MFMAs and across the
+  // pipeline drain; store_tile_bf16 keeps two block rows of it in flight from then on (gemm_epilogue.hpp).  Only in instantiations
+  // whose accumulators leave room for two block rows; the others fetch it in place.
+  constexpr bool BF16OUT = !SPLITK && sizeof(OutT) == 2;
+  constexpr int AHEAD = (BF16OUT && MI * NI * 16 + 2 * Staging<NI>::CHUNKS * 4 <= 128) ? 2 : 0;
+  typedef AuxAhead<NI, EPI, AHEAD> Ahead;
+  Ahead ahead;
+  if constexpr (Ahead::ON) load_aux_rows<Staging<NI>::CHUNKS, Staging<NI>::CPR>(p, m0 + wm * WROWS, n0 + wn * WCOLS, lane, ahead.v[0]);
   wait_vm<0>();
   __builtin_amdgcn_s_barrier();
 #undef GOAT_ISSUE
@@ -532,158 +471,13 @@ __device__ __forceinline__ void gemm2_tile(const G2Args& p, int bid, int split) 
     return;
   }
   const int wrow0 = wm * WROWS, wcol0 = wn * WCOLS;
-  if (SPLITK) {
-    float* C = reinterpret_cast<float*>(p.C);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        const int col = n0 + wcol0 + j * 32 + l31;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + wrow0 + i * 32 + c_row(r, lane);
-          if (row < p.M && col < p.N) atomicAdd(C + (int64_t)row * p.ldc + col, acc[i][j][r]);
-        }
-      }
-    return;
-  }
-  if (sizeof(OutT) == 4) {  // f32 output: 32 lanes = 128 contiguous bytes per row, store straight from the accumulators
-    float* C = reinterpret_cast<float*>(p.C);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        const int col = n0 + wcol0 + j * 32 + l31;
-        const float bcol = (p.bias != nullptr && col < p.N) ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + wrow0 + i * 32 + c_row(r, lane);
-          if (row < p.M && col < p.N) {
-            float* dst = C + (int64_t)row * p.ldc + col;
-            const float u = acc[i][j][r] + bcol;
-            if (p.accum) *dst = u + *dst;
-            else if (GOAT_G2_STORE) __builtin_nontemporal_store(u, dst);      // streamed out of L2 (see store16)
-            else *dst = u;
-          }
-        }
-      }
-    return;
-  }
-  // bf16 output.  The MFMA operand roles are swapped for these kernels (SWAP: D = B·A^T, i.e. lane = row of C, the 16
-  // registers of a block = 4 groups of 4 consecutive columns), so a lane packs 4 results into 8 bytes.  Each wave stages
-  // one 32-row block row of its patch at a time through its OWN slice of the (now free) LDS ring — no workgroup barrier:
-  // a wave starts storing the moment its last MFMA retires — and writes it out as whole rows of the patch (128-B / 192-B
-  // segments, 16 B per lane).  Round 1 staged the whole tile with 2-byte LDS writes between two __syncthreads():
-  // 9.6 of the 26.8 us of the 3840x3072x768 launch (profiles/round2_gemm_epilogue_ab.txt).
-  typedef bf16_t T;
-  constexpr int EPC = 8;
-  constexpr int RBY = WCOLS * 2 + 16;          // staging row stride in bytes (16 B pad: the 8-byte writes of 16 rows hit 16 bank pairs)
-  constexpr int WSLICE = 32 * RBY;             // per-wave staging slice: 4.5 KiB (64 columns) / 6.5 KiB (96)
-  static_assert(NW * WSLICE <= NSTAGE * STAGE, "per-wave epilogue slices must fit the LDS ring");
-  constexpr int CPR = WCOLS / EPC;             // 16-byte chunks per patch row
-  constexpr int CHUNKS = 32 * CPR / 64;        // chunks per lane and block row
-  static_assert(32 * CPR % 64 == 0, "a block row is a whole number of 16-byte chunks per lane");
-  constexpr bool DACT = (EPI == GOAT_EPI_MUL_DGELU || EPI == GOAT_EPI_MUL_DRELU);
-  constexpr bool ACT = (EPI == GOAT_EPI_GELU || EPI == GOAT_EPI_RELU);
-  T* aux = reinterpret_cast<T*>(p.aux);
-  T* C = reinterpret_cast<T*>(p.C);
-  const bool c_vec = (p.ldc % EPC) == 0 && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
-  const bool aux_vec = aux != nullptr && (p.ldaux % EPC) == 0 && ((reinterpret_cast<uintptr_t>(aux) & 15) == 0);
-  const uint32_t ws = smem_base + wave * WSLICE;                 // this wave's slice (LDS byte address)
-  char* wsp = smem + wave * WSLICE;
-  const int col_w = n0 + wn * WCOLS;                             // first column of the wave patch
-  // bias of this lane's columns: block j, group q -> columns j*32 + 4*hi + 8*q + {0..3}
-  f32x4 bv[NI][4];
-#pragma unroll
-  for (int j = 0; j < NI; ++j)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int col = col_w + j * 32 + 4 * hi + 8 * q;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) bv[j][q][e] = (p.bias != nullptr && col + e < p.N) ? p.bias[col + e] : 0.f;
-    }
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int row_w = m0 + wm * WROWS + i * 32;                  // first row of this block row
-    if (DACT) {
-      // the saved pre-activation block row (fetched one block row ahead, see above) -> slice -> each lane picks up its own
-      // 4-column groups; the next block row's loads are issued first and stay in flight behind this one's arithmetic and stores
-      if constexpr (PF_) {
-        if (i + 1 < MI) load_aux_rows<CHUNKS, CPR>(p, row_w + 32, col_w, lane, auxr.row((i + 1) & 1));
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c) {
-          const int idx = c * 64 + lane, r = idx / CPR, cc = idx % CPR;
-          *reinterpret_cast<uint4*>(wsp + r * RBY + cc * 16) = auxr.row(i & 1)[c];
-        }
-      } else {           // large accumulator tiles: the block row is fetched where it is used (round-2 behaviour)
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c) {
-          const int idx = c * 64 + lane, r = idx / CPR, cc = idx % CPR;
-          uint4 now;
-          load_aux_rows<1, CPR>(p, row_w, col_w, idx, &now);     // (chunk c of this lane = chunk 0 of "lane" idx)
-          *reinterpret_cast<uint4*>(wsp + r * RBY + cc * 16) = now;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // same-wave LDS hand-over between lanes
-    }
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        char* slot = wsp + l31 * RBY + (j * 32 + 4 * hi + 8 * q) * 2;
-        float u[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = acc[i][j][4 * q + e] + bv[j][q][e];
-        if (DACT) {
-          const bf16x4 a4 = *reinterpret_cast<const bf16x4*>(slot);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float av = (float)a4[e];
-            u[e] = (EPI == GOAT_EPI_MUL_DGELU) ? u[e] * dgelu_fast(av) : (av > 0.f ? u[e] : 0.f);
-          }
-        }
-        bf16x4 o4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o4[e] = (bf16_t)u[e];
-        *reinterpret_cast<bf16x4*>(slot) = o4;
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // same-wave LDS hand-over between lanes
-    // write-out: whole patch rows, 16 bytes per lane.  Activation epilogues store the staged pre-activation to `aux` (if
-    // given) and the activation of the same bf16 values to C from this one pass.
-#pragma unroll
-    for (int c = 0; c < CHUNKS; ++c) {
-      const int idx = c * 64 + lane, r = idx / CPR, cc = idx % CPR;
-      const int row = row_w + r, col = col_w + cc * EPC;
-      uint4 raw = *reinterpret_cast<const uint4*>(wsp + r * RBY + cc * 16);
-      if (row >= p.M || col >= p.N) continue;
-      if (ACT) {
-        if (aux != nullptr) {
-          if (col + EPC <= p.N && aux_vec) {
-            store16(aux + (int64_t)row * p.ldaux + col, raw);
-          } else {
-            const T* rv = reinterpret_cast<const T*>(&raw);
-            for (int e = 0; e < EPC; ++e)
-              if (col + e < p.N) aux[(int64_t)row * p.ldaux + col + e] = rv[e];
-          }
-        }
-        bf16x8 v = *reinterpret_cast<bf16x8*>(&raw);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-          const float u = (float)v[e];
-          const float h = (EPI == GOAT_EPI_GELU) ? gelu_fast(u) : fmaxf(u, 0.f);
-          v[e] = (bf16_t)h;
-        }
-        raw = *reinterpret_cast<uint4*>(&v);
-      }
-      if (col + EPC <= p.N && c_vec) {
-        store16(C + (int64_t)row * p.ldc + col, raw);
-      } else {
-        const T* rv = reinterpret_cast<const T*>(&raw);
-        for (int e = 0; e < EPC; ++e)
-          if (col + e < p.N) C[(int64_t)row * p.ldc + col + e] = rv[e];
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // same-wave LDS hand-over between lanes      // the slice is rewritten by the next block row
+  if constexpr (!BF16OUT) {
+    // (patch origin: wave-uniform — `wave` went through readfirstlane, m0 / n0 come from the block id; no PIN here, see store_tile_f32)
+    store_tile_f32<MI, NI, SPLITK, GOAT_G2_STORE != 0, false>(p, accs, m0 + wrow0, n0 + wcol0, lane);
+  } else {
+    // each wave stages through its own slice of the (now free) LDS ring
+    static_assert(NW * Staging<NI>::WSLICE <= NSTAGE * STAGE, "per-wave epilogue slices must fit the LDS ring");
+    store_tile_bf16<MI, NI, EPI, AHEAD, (Ahead::ON ? 1 : 0)>(p, accs, smem + wave * Staging<NI>::WSLICE, m0 + wrow0, n0 + wcol0, lane, ahead);
   }
 #endif  // __HIP_DEVICE_COMPILE__
 }
@@ -772,6 +566,19 @@ int launch2(hipStream_t st, const G2Args& a, int split, int nstage) {
   return GOAT_E_ARG;
 }
 
+// runtime epilogue id of a bf16 launch -> template constant: f(std::integral_constant<int, GOAT_EPI_...>) (host side)
+template <class F>
+int with_epilogue(int epi, F&& f) {
+  switch (epi) {
+    case GOAT_EPI_NONE: return f(std::integral_constant<int, GOAT_EPI_NONE>());
+    case GOAT_EPI_GELU: return f(std::integral_constant<int, GOAT_EPI_GELU>());
+    case GOAT_EPI_RELU: return f(std::integral_constant<int, GOAT_EPI_RELU>());
+    case GOAT_EPI_MUL_DGELU: return f(std::integral_constant<int, GOAT_EPI_MUL_DGELU>());
+    case GOAT_EPI_MUL_DRELU: return f(std::integral_constant<int, GOAT_EPI_MUL_DRELU>());
+  }
+  return GOAT_E_ARG;
+}
+
 template <class CF, bool TA, bool TB>
 int dispatch2(hipStream_t st, const G2Args& a, int dtype_out, int epi, int split, int nstage) {
   if (split > 1) return launch2<CF, TA, TB, float, GOAT_EPI_NONE, true>(st, a, split, nstage);
@@ -783,14 +590,7 @@ int dispatch2(hipStream_t st, const G2Args& a, int dtype_out, int epi, int split
     if (epi != GOAT_EPI_NONE) return GOAT_E_ARG;      // forward / dgrad; not instantiating them saves a quarter of the build)
     return launch2<CF, TA, TB, bf16_t, GOAT_EPI_NONE, false>(st, a, 1, nstage);
   }
-  switch (epi) {
-    case GOAT_EPI_NONE: return launch2<CF, TA, TB, bf16_t, GOAT_EPI_NONE, false>(st, a, 1, nstage);
-    case GOAT_EPI_GELU: return launch2<CF, TA, TB, bf16_t, GOAT_EPI_GELU, false>(st, a, 1, nstage);
-    case GOAT_EPI_RELU: return launch2<CF, TA, TB, bf16_t, GOAT_EPI_RELU, false>(st, a, 1, nstage);
-    case GOAT_EPI_MUL_DGELU: return launch2<CF, TA, TB, bf16_t, GOAT_EPI_MUL_DGELU, false>(st, a, 1, nstage);
-    case GOAT_EPI_MUL_DRELU: return launch2<CF, TA, TB, bf16_t, GOAT_EPI_MUL_DRELU, false>(st, a, 1, nstage);
-  }
-  return GOAT_E_ARG;
+  return with_epilogue(epi, [&](auto e) { return launch2<CF, TA, TB, bf16_t, decltype(e)::value, false>(st, a, 1, nstage); });
 }
 
 // all operand layouts a tile supports (transposed operands need a power-of-two tile width on that side)

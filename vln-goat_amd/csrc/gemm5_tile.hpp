@@ -1,7 +1,9 @@
 // Device code of the "ping-pong" bf16 MFMA GEMM tile for gfx950 (goat_gemm_bf16 / goat_wgrad_grouped with nstage | GOAT_GEMM_PP).
 //
-//   C[M,N] = epilogue( op(A) · op(B)^T ),  same operand layouts, argument block (G2Args), tile order and epilogues as
-//   gemm2_tile.hpp; what differs is the main loop.
+//   C[M,N] = epilogue( op(A) · op(B)^T ),  same operand layouts, argument block (G2Args) and tile order as gemm2_tile.hpp, same result
+//   stores (gemm_epilogue.hpp); what differs is the main loop.  The stores' parameters here: staging slice `wave` of the free LDS
+//   (pp_tile) or a slice relocated out of the next tile's DMA targets (pp_tiles_persist); 3 block rows of the saved pre-activation in
+//   flight for the x act' epilogues (2 for the persistent 256 x 256 tile); float32 stores always non-temporal.
 //
 // Why a second main loop.  gemm2_tile.hpp runs its eight waves in lockstep: one s_barrier per K-tile, after which every wave
 // first issues its LDS-DMA and fragment reads and then its MFMAs.  The two waves that share a SIMD therefore want the memory
@@ -33,6 +35,7 @@
 // at least one full MFMA phase (>= 1024 cycles on 256 x 256) in flight before anyone waits for it.
 #pragma once
 #include "gemm2_tile.hpp"
+#include "gemm_epilogue.hpp"
 
 namespace goat_g5 {
 using namespace goat_g2;
@@ -242,7 +245,8 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
     else vb[x] = BB::frag_lane(lane, wn * NI + (x < NI ? x : 0)) + B_BASE;
   }
 
-  f32x16 acc[MI][NI];
+  AccTile<MI, NI> accs;
+  f32x16 (&acc)[MI][NI] = accs.t;
 #pragma unroll
   for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -528,149 +532,14 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
       if (hi == 0 && row < p.M) atomicAdd(p.colsum + row, v);
     }
   }
-  if (SPLITK) {
-    float* C = reinterpret_cast<float*>(p.C);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        const int col = n0 + wcol0 + j * 32 + l31;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + wrow0 + i * 32 + c_row(r, lane);
-          if (row < p.M && col < p.N) atomicAdd(C + (int64_t)row * p.ldc + col, acc[i][j][r]);
-        }
-      }
-    return;
-  }
-  if (sizeof(OutT) == 4) {
-    float* C = reinterpret_cast<float*>(p.C);
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) {
-        const int col = n0 + wcol0 + j * 32 + l31;
-        const float bcol = (p.bias != nullptr && col < p.N) ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = m0 + wrow0 + i * 32 + c_row(r, lane);
-          if (row < p.M && col < p.N) {
-            float* dst = C + (int64_t)row * p.ldc + col;
-            const float u = acc[i][j][r] + bcol;
-            if (p.accum) *dst = u + *dst;
-            else __builtin_nontemporal_store(u, dst);
-          }
-        }
-      }
-    return;
-  }
-  // bf16 output: as gemm2_tile.hpp — swapped MFMA operand roles (lane = row of C, 4 consecutive columns per register group),
-  // staged one 32-row block row at a time through the wave's own slice of the free LDS, written out as 16-byte row pieces.
-  typedef bf16_t T;
-  constexpr int EPC = 8;
-  constexpr int RBY = WCOLS * 2 + 16;
-  constexpr int WSLICE = 32 * RBY;
-  static_assert(8 * WSLICE <= CF::SMEM, "per-wave epilogue slices must fit the LDS ring");
-  constexpr int CPR = WCOLS / EPC;
-  constexpr int CHUNKS = 32 * CPR / 64;
-  static_assert(32 * CPR % 64 == 0, "a block row is a whole number of 16-byte chunks per lane");
-  constexpr bool DACT = (EPI == GOAT_EPI_MUL_DGELU || EPI == GOAT_EPI_MUL_DRELU);
-  constexpr bool ACT = (EPI == GOAT_EPI_GELU || EPI == GOAT_EPI_RELU);
-  T* aux = reinterpret_cast<T*>(p.aux);
-  T* C = reinterpret_cast<T*>(p.C);
-  const bool c_vec = (p.ldc % EPC) == 0 && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
-  const bool aux_vec = aux != nullptr && (p.ldaux % EPC) == 0 && ((reinterpret_cast<uintptr_t>(aux) & 15) == 0);
-  char* wsp = smem + wave * WSLICE;
-  const int col_w = n0 + wcol0;
-  f32x4 bv[DACT ? 1 : NI][4];          // (the activation-derivative epilogues take no bias: C = (A·B) * act'(aux))
-  if (!DACT) {
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int col = col_w + j * 32 + 4 * hi + 8 * q;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bv[j][q][e] = (p.bias != nullptr && col + e < p.N) ? p.bias[col + e] : 0.f;
-      }
-  }
-  // activation-derivative epilogues (FFN dgrad): the saved pre-activation of the wave patch is fetched up to three block rows AHEAD, into
-  // the registers the fragments occupied until the last MFMA phase (CHUNKS 16-byte pieces per lane and block row): one exposed HBM
-  // round trip per tile instead of one per block row (the first version of this epilogue: 20480 x 3072 x 768 at 548 TFLOP/s against
-  // 771 with the GELU epilogue).  Four rows at once would not fit beside the 128 accumulator registers of the 256 x 256 tile.
-  constexpr int AD = MI < 3 ? MI : 3;
-  uint4 auxv[DACT ? AD : 1][CHUNKS];
-  if (DACT) {
-#pragma unroll
-    for (int i = 0; i < AD; ++i) load_aux_rows<CHUNKS, CPR>(p, m0 + wrow0 + i * 32, col_w, lane, auxv[i]);
-  }
-#pragma unroll
-  for (int i = 0; i < MI; ++i) {
-    const int row_w = m0 + wrow0 + i * 32;
-    if (DACT) {
-#pragma unroll
-      for (int c = 0; c < CHUNKS; ++c) {
-        const int idx = c * 64 + lane, r = idx / CPR, cc = idx % CPR;
-        *reinterpret_cast<uint4*>(wsp + r * RBY + cc * 16) = auxv[DACT ? i % AD : 0][c];
-      }
-      if (i + AD < MI) load_aux_rows<CHUNKS, CPR>(p, row_w + AD * 32, col_w, lane, auxv[DACT ? i % AD : 0]);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        char* slot = wsp + l31 * RBY + (j * 32 + 4 * hi + 8 * q) * 2;
-        float u[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = DACT ? acc[i][j][4 * q + e] : acc[i][j][4 * q + e] + bv[DACT ? 0 : j][q][e];
-        if (DACT) {
-          const bf16x4 a4 = *reinterpret_cast<const bf16x4*>(slot);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float av = (float)a4[e];
-            u[e] = (EPI == GOAT_EPI_MUL_DGELU) ? u[e] * dgelu_fast(av) : (av > 0.f ? u[e] : 0.f);
-          }
-        }
-        bf16x4 o4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o4[e] = (bf16_t)u[e];
-        *reinterpret_cast<bf16x4*>(slot) = o4;
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int c = 0; c < CHUNKS; ++c) {
-      const int idx = c * 64 + lane, r = idx / CPR, cc = idx % CPR;
-      const int row = row_w + r, col = col_w + cc * EPC;
-      uint4 raw = *reinterpret_cast<const uint4*>(wsp + r * RBY + cc * 16);
-      if (row >= p.M || col >= p.N) continue;
-      if (ACT) {
-        if (aux != nullptr) {
-          if (col + EPC <= p.N && aux_vec) {
-            store16(aux + (int64_t)row * p.ldaux + col, raw);
-          } else {
-            const T* rv = reinterpret_cast<const T*>(&raw);
-            for (int e = 0; e < EPC; ++e)
-              if (col + e < p.N) aux[(int64_t)row * p.ldaux + col + e] = rv[e];
-          }
-        }
-        bf16x8 v = *reinterpret_cast<bf16x8*>(&raw);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-          const float u = (float)v[e];
-          const float h = (EPI == GOAT_EPI_GELU) ? gelu_fast(u) : fmaxf(u, 0.f);
-          v[e] = (bf16_t)h;
-        }
-        raw = *reinterpret_cast<uint4*>(&v);
-      }
-      if (col + EPC <= p.N && c_vec) {
-        store16(C + (int64_t)row * p.ldc + col, raw);
-      } else {
-        const T* rv = reinterpret_cast<const T*>(&raw);
-        for (int e = 0; e < EPC; ++e)
-          if (col + e < p.N) C[(int64_t)row * p.ldc + col + e] = rv[e];
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if constexpr (SPLITK || sizeof(OutT) == 4) {
+    // (PIN: the patch origin passed here must stay wave-uniform — `wave` went through readfirstlane, m0 / n0 come from the tile position)
+    store_tile_f32<MI, NI, SPLITK, true, true>(p, accs, m0 + wrow0, n0 + wcol0, lane);
+  } else {
+    // x act' epilogues: up to three block rows of the saved pre-activation in flight, in the registers the fragments occupied until the
+    // last MFMA phase.  Four rows at once would not fit beside the 128 accumulator registers of the 256 x 256 tile.
+    static_assert(8 * Staging<NI>::WSLICE <= CF::SMEM, "per-wave epilogue slices must fit the LDS ring");
+    store_tile_bf16<MI, NI, EPI, 3>(p, accs, smem + wave * Staging<NI>::WSLICE, m0 + wrow0, n0 + wcol0, lane);
   }
 #endif  // __HIP_DEVICE_COMPILE__
 }
@@ -805,14 +674,7 @@ int pp_dispatch2(hipStream_t st, const G2Args& a, int dtype_out, int epi, int sp
     if (epi != GOAT_EPI_NONE) return GOAT_E_ARG;
     return pp_launch<CF, TA, TB, bf16_t, GOAT_EPI_NONE, false>(st, a, 1);
   } else {
-    switch (epi) {
-      case GOAT_EPI_NONE: return pp_launch<CF, TA, TB, bf16_t, GOAT_EPI_NONE, false>(st, a, 1);
-      case GOAT_EPI_GELU: return pp_launch<CF, TA, TB, bf16_t, GOAT_EPI_GELU, false>(st, a, 1);
-      case GOAT_EPI_RELU: return pp_launch<CF, TA, TB, bf16_t, GOAT_EPI_RELU, false>(st, a, 1);
-      case GOAT_EPI_MUL_DGELU: return pp_launch<CF, TA, TB, bf16_t, GOAT_EPI_MUL_DGELU, false>(st, a, 1);
-      case GOAT_EPI_MUL_DRELU: return pp_launch<CF, TA, TB, bf16_t, GOAT_EPI_MUL_DRELU, false>(st, a, 1);
-    }
-    return GOAT_E_ARG;
+    return with_epilogue(epi, [&](auto e) { return pp_launch<CF, TA, TB, bf16_t, decltype(e)::value, false>(st, a, 1); });
   }
 }
 
@@ -909,7 +771,6 @@ __device__ __forceinline__ void pp_tiles_persist(const G2Args& p, int pos0, int 
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int grp = wave >> 2, wn = wave & 3;
-  const int hi = lane >> 5, l31 = lane & 31;
   const int nkt = (p.Kc + BK - 1) / BK;
 
   __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, (int)p.a_bytes, 0x00020000);
@@ -922,7 +783,8 @@ __device__ __forceinline__ void pp_tiles_persist(const G2Args& p, int pos0, int 
     if (!TB) vb[x] = BB::frag_lane(lane, x) + (uint32_t)(wn * WCOLS * 128) + B_BASE;
     else vb[x] = BB::frag_lane(lane, wn * NI + (x < NI ? x : 0)) + B_BASE;
   }
-  f32x16 acc[MI][NI];
+  AccTile<MI, NI> accs;
+  f32x16 (&acc)[MI][NI] = accs.t;
   bf16x8 fa[4][MI], fb[4][NI];
   constexpr bool do_colsum = false;
   float bsum[MI];
@@ -1026,22 +888,11 @@ __device__ __forceinline__ void pp_tiles_persist(const G2Args& p, int pos0, int 
     if (nkt > 1) PP_ISSUE_A(org0, 0, 1, 1, 0, PPW_A);
   }
 
-  // epilogue staging (see the header comment): wave-private slices outside the next tile's first DMA targets
-  typedef bf16_t T;
-  constexpr int EPC = 8;
-  constexpr int RBY = WCOLS * 2 + 16;
-  constexpr int WSLICE = 32 * RBY;
+  // epilogue staging (see the comment above): wave-private slices outside the next tile's first DMA targets
+  constexpr int WSLICE = Staging<NI>::WSLICE;
   constexpr int NFIT = BSZ / WSLICE < 8 ? BSZ / WSLICE : 8;
   static_assert((8 - NFIT) * WSLICE <= AH, "the staging slices that do not fit B buffer 1 must fit A_1 buffer 1");
   char* wsp = wave < NFIT ? smem + B_BASE + BSZ + wave * WSLICE : smem + 3 * AH + (wave - NFIT) * WSLICE;
-  constexpr int CPR = WCOLS / EPC;
-  constexpr int CHUNKS = 32 * CPR / 64;
-  constexpr bool DACT = (EPI == GOAT_EPI_MUL_DGELU || EPI == GOAT_EPI_MUL_DRELU);
-  constexpr bool ACT = (EPI == GOAT_EPI_GELU || EPI == GOAT_EPI_RELU);
-  T* aux = reinterpret_cast<T*>(p.aux);
-  T* C = reinterpret_cast<T*>(p.C);
-  const bool c_vec = (p.ldc % EPC) == 0 && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
-  const bool aux_vec = aux != nullptr && (p.ldaux % EPC) == 0 && ((reinterpret_cast<uintptr_t>(aux) & 15) == 0);
   const int wrow0 = grp * WROWS, wcol0 = wn * WCOLS;
 
   for (int pos = pos0; pos < pos_end; pos += pos_step) {
@@ -1098,96 +949,9 @@ __device__ __forceinline__ void pp_tiles_persist(const G2Args& p, int pos0, int 
       }
     }
 
-    // ---- epilogue of tile (m0, n0): pp_tile's bf16 epilogue on the relocated staging slices
-    {
-      const int col_w = n0 + wcol0;
-      f32x4 bv[DACT ? 1 : NI][4];
-      if (!DACT) {
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int col = col_w + j * 32 + 4 * hi + 8 * q;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bv[j][q][e] = (p.bias != nullptr && col + e < p.N) ? p.bias[col + e] : 0.f;
-          }
-      }
-      constexpr int AD = MI < 3 ? MI : (MI == 4 ? 2 : 3);      // (256 x 256: three rows ahead spill beside the persistent loop's extra state)
-      uint4 auxv[DACT ? AD : 1][CHUNKS];
-      if (DACT) {
-#pragma unroll
-        for (int i = 0; i < AD; ++i) load_aux_rows<CHUNKS, CPR>(p, m0 + wrow0 + i * 32, col_w, lane, auxv[i]);
-      }
-#pragma unroll
-      for (int i = 0; i < MI; ++i) {
-        const int row_w = m0 + wrow0 + i * 32;
-        if (DACT) {
-#pragma unroll
-          for (int c = 0; c < CHUNKS; ++c) {
-            const int idx = c * 64 + lane, r = idx / CPR, cc = idx % CPR;
-            *reinterpret_cast<uint4*>(wsp + r * RBY + cc * 16) = auxv[DACT ? i % AD : 0][c];
-          }
-          if (i + AD < MI) load_aux_rows<CHUNKS, CPR>(p, row_w + AD * 32, col_w, lane, auxv[DACT ? i % AD : 0]);
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            char* slot = wsp + l31 * RBY + (j * 32 + 4 * hi + 8 * q) * 2;
-            float u[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = DACT ? acc[i][j][4 * q + e] : acc[i][j][4 * q + e] + bv[DACT ? 0 : j][q][e];
-            if (DACT) {
-              const bf16x4 a4 = *reinterpret_cast<const bf16x4*>(slot);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const float av = (float)a4[e];
-                u[e] = (EPI == GOAT_EPI_MUL_DGELU) ? u[e] * dgelu_fast(av) : (av > 0.f ? u[e] : 0.f);
-              }
-            }
-            bf16x4 o4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o4[e] = (bf16_t)u[e];
-            *reinterpret_cast<bf16x4*>(slot) = o4;
-          }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int c = 0; c < CHUNKS; ++c) {
-          const int idx = c * 64 + lane, r = idx / CPR, cc = idx % CPR;
-          const int row = row_w + r, col = col_w + cc * EPC;
-          uint4 raw = *reinterpret_cast<const uint4*>(wsp + r * RBY + cc * 16);
-          if (row >= p.M || col >= p.N) continue;
-          if (ACT) {
-            if (aux != nullptr) {
-              if (col + EPC <= p.N && aux_vec) {
-                store16(aux + (int64_t)row * p.ldaux + col, raw);
-              } else {
-                const T* rv = reinterpret_cast<const T*>(&raw);
-                for (int e = 0; e < EPC; ++e)
-                  if (col + e < p.N) aux[(int64_t)row * p.ldaux + col + e] = rv[e];
-              }
-            }
-            bf16x8 v = *reinterpret_cast<bf16x8*>(&raw);
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) {
-              const float u = (float)v[e];
-              const float h = (EPI == GOAT_EPI_GELU) ? gelu_fast(u) : fmaxf(u, 0.f);
-              v[e] = (bf16_t)h;
-            }
-            raw = *reinterpret_cast<uint4*>(&v);
-          }
-          if (col + EPC <= p.N && c_vec) {
-            store16(C + (int64_t)row * p.ldc + col, raw);
-          } else {
-            const T* rv = reinterpret_cast<const T*>(&raw);
-            for (int e = 0; e < EPC; ++e)
-              if (col + e < p.N) C[(int64_t)row * p.ldc + col + e] = rv[e];
-          }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-    }
+    // ---- epilogue of tile (m0, n0), on the relocated staging slices (256 x 256: three block rows of the saved pre-activation in
+    //      flight spill beside this loop's extra state, two do not)
+    store_tile_bf16<MI, NI, EPI, (MI == 4 ? 2 : 3)>(p, accs, wsp, m0 + wrow0, n0 + wcol0, lane);
     m0 = nm0;
     n0 = nn0;
   }
@@ -1240,24 +1004,8 @@ int pp_launch_persist(hipStream_t st, const G2Args& a) {
 template <class CF>
 int pp_dispatch_persist(hipStream_t st, const G2Args& a, int trans_a, int trans_b, int dtype_out, int epi, int split) {
   if (trans_a || split > 1 || dtype_out != GOAT_BF16) return GOAT_E_ARG;
-  if (!trans_b) {
-    switch (epi) {
-      case GOAT_EPI_NONE: return pp_launch_persist<CF, false, GOAT_EPI_NONE>(st, a);
-      case GOAT_EPI_GELU: return pp_launch_persist<CF, false, GOAT_EPI_GELU>(st, a);
-      case GOAT_EPI_RELU: return pp_launch_persist<CF, false, GOAT_EPI_RELU>(st, a);
-      case GOAT_EPI_MUL_DGELU: return pp_launch_persist<CF, false, GOAT_EPI_MUL_DGELU>(st, a);
-      case GOAT_EPI_MUL_DRELU: return pp_launch_persist<CF, false, GOAT_EPI_MUL_DRELU>(st, a);
-    }
-  } else {
-    switch (epi) {
-      case GOAT_EPI_NONE: return pp_launch_persist<CF, true, GOAT_EPI_NONE>(st, a);
-      case GOAT_EPI_GELU: return pp_launch_persist<CF, true, GOAT_EPI_GELU>(st, a);
-      case GOAT_EPI_RELU: return pp_launch_persist<CF, true, GOAT_EPI_RELU>(st, a);
-      case GOAT_EPI_MUL_DGELU: return pp_launch_persist<CF, true, GOAT_EPI_MUL_DGELU>(st, a);
-      case GOAT_EPI_MUL_DRELU: return pp_launch_persist<CF, true, GOAT_EPI_MUL_DRELU>(st, a);
-    }
-  }
-  return GOAT_E_ARG;
+  if (!trans_b) return with_epilogue(epi, [&](auto e) { return pp_launch_persist<CF, false, decltype(e)::value>(st, a); });
+  return with_epilogue(epi, [&](auto e) { return pp_launch_persist<CF, true, decltype(e)::value>(st, a); });
 }
 
 }  // namespace goat_g5
