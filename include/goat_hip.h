@@ -214,6 +214,32 @@ int goat_attn_bwd(void* stream, int dtype,
                   int B, int nh, int Lq, int Lk, float scale,
                   float p, uint64_t seed, uint64_t offset, const uint64_t* rng_dev);
 
+/* goat_attn_fwd / goat_attn_bwd for 1 <= Lk <= 512 (RxR-length instructions: max_txt_len 300, at most max_position_embeddings - 2 = 512
+ * tokens): same arguments, same meaning of every output, same dropout bits.  The forward streams the keys in tiles of 32 with a running
+ * row maximum / row sum (csrc/attention_long.hip) instead of holding the score row-block in registers; the backward runs goat_attn_bwd's
+ * general dQ and dK|dV kernels with all K rows in LDS.  GOAT_E_SHAPE for Lk > 512 or a stride / base that is not 16-byte aligned
+ * (O included: the output rows are written in 4-element vectors).  goat_attn_fwd / goat_attn_bwd keep their Lk <= 256 contract. */
+int goat_attn_long_fwd(void* stream, int dtype,
+                       const void* Q, int64_t q_rs, int64_t q_bs,
+                       const void* K, int64_t k_rs, int64_t k_bs,
+                       const void* V, int64_t v_rs, int64_t v_bs,
+                       void* O, int64_t o_rs, int64_t o_bs,
+                       const float* kmask, const float* bias, float* lse,
+                       int B, int nh, int Lq, int Lk, float scale,
+                       float p, uint64_t seed, uint64_t offset, const uint64_t* rng_dev);
+int goat_attn_long_bwd(void* stream, int dtype,
+                       const void* Q, int64_t q_rs, int64_t q_bs,
+                       const void* K, int64_t k_rs, int64_t k_bs,
+                       const void* V, int64_t v_rs, int64_t v_bs,
+                       const void* O, int64_t o_rs, int64_t o_bs,
+                       const void* dO, int64_t do_rs, int64_t do_bs,
+                       void* dQ, int64_t dq_rs, int64_t dq_bs,
+                       void* dK, int64_t dk_rs, int64_t dk_bs,
+                       void* dV, int64_t dv_rs, int64_t dv_bs,
+                       const float* kmask, const float* bias, const float* lse, float* dbias,
+                       int B, int nh, int Lq, int Lk, float scale,
+                       float p, uint64_t seed, uint64_t offset, const uint64_t* rng_dev);
+
 /* Softmax cross-entropy (reduction none) on float32 logits [M, ld] with N valid columns (ld >= N may be padded):
  * loss[m] = logsumexp(logits[m,:N]) - logits[m,target[m]], lse saved.  Replaces F.cross_entropy on the 576 x 50265
  * MLM scores (P/model/pretrain_goat.py:213-215).  Backward writes dlogits (GOAT_BF16 or GOAT_F32) with row stride

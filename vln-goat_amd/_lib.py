@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('GOAT_HIP_LIB') or os.path.join(CSRC, 'libgoat_hip.so')     # (override: kernel A/B experiments)
-SOURCES = ['gemm.hip', 'gemm2.hip', 'gemm3.hip', 'gemm5.hip', 'attention.hip', 'attention2.hip', 'rowops.hip', 'causal.hip', 'optim.hip', 'glue.hip']
+SOURCES = ['gemm.hip', 'gemm2.hip', 'gemm3.hip', 'gemm5.hip', 'attention.hip', 'attention2.hip', 'attention_long.hip', 'rowops.hip', 'causal.hip', 'optim.hip', 'glue.hip']
 
 GOAT_F32, GOAT_BF16 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_ACCUM = 0, 1, 2, 3, 4, 5
@@ -46,6 +46,8 @@ SIGNATURES = {
     'goat_act_bwd': [_vp, _i32, _vp, _vp, _vp, _i64, _i32, _f32, _u64, _u64, _vp],
     'goat_attn_fwd': [_vp, _i32] + [_vp, _i64, _i64] * 4 + [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _u64, _vp],
     'goat_attn_bwd': [_vp, _i32] + [_vp, _i64, _i64] * 8 + [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _u64, _vp],
+    'goat_attn_long_fwd': [_vp, _i32] + [_vp, _i64, _i64] * 4 + [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _u64, _vp],
+    'goat_attn_long_bwd': [_vp, _i32] + [_vp, _i64, _i64] * 8 + [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _u64, _vp],
     'goat_ce_fwd': [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp],
     'goat_ce_bwd': [_vp, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64],
     'goat_pano_fusion_fwd': [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32],
@@ -106,7 +108,7 @@ def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into csrc/libgoat_hip.so (in-tree, travels with the repo snapshot)."""
     force = force or os.environ.get('GOAT_FORCE_BUILD', '0') == '1'
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'gemm2_tile.hpp'), os.path.join(CSRC, 'gemm5_tile.hpp'), os.path.join(CSRC, 'gemm_epilogue.hpp'), os.path.join(CSRC, 'gemm_args.hpp'), os.path.join(CSRC, 'attn_args.hpp'), os.path.join(_HERE, '..', 'include', 'goat_hip.h')]
+    deps = srcs + [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'gemm2_tile.hpp'), os.path.join(CSRC, 'gemm5_tile.hpp'), os.path.join(CSRC, 'gemm_epilogue.hpp'), os.path.join(CSRC, 'gemm_args.hpp'), os.path.join(CSRC, 'attn_args.hpp'), os.path.join(CSRC, 'attn_tile.hpp'), os.path.join(_HERE, '..', 'include', 'goat_hip.h')]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         LAST_BUILD[0] = 'reused (library newer than every source; GOAT_FORCE_BUILD=1 or build(force=True) recompiles)'
         return LIB_PATH

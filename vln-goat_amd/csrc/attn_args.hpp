@@ -1,5 +1,5 @@
-// Argument block shared by the attention kernels (attention.hip: one wave per tile, any dtype / length; attention2.hip: the
-// LDS-staged bf16 kernels for sequences of up to 128 rows).
+// Argument block shared by the attention kernels (attention.hip: one wave per tile, any dtype, Lk <= 256; attention2.hip: the
+// LDS-staged bf16 kernels for sequences of up to 128 rows; attention_long.hip: the key-streaming forward for Lk <= 512).
 #pragma once
 #include "common.hpp"
 
@@ -20,3 +20,7 @@ struct AttnArgs {
 // attention2.hip; return GOAT_E_SHAPE when the problem is outside their range (the caller then uses the general kernels)
 int goat_attn2_fwd(hipStream_t st, const AttnArgs& a);
 int goat_attn2_bwd(hipStream_t st, const AttnArgs& a);
+
+// attention.hip: its dQ and dK|dV kernels for a checked problem of any Lk whose K rows fit the LDS (their register arrays do not
+// depend on the length; attention_long.hip runs them for Lk <= 512)
+int goat_attn_tile_bwd(hipStream_t st, const AttnArgs& a, int dtype);

@@ -31,7 +31,7 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 //        (2) per (b, 256-column slab): softmax over the L scores, out[cols] = tanh(sum_l a_l x[l,cols])
 //   bwd  (1) da[b,l] = x_l·du,  du = dout (1 - out^2)   one wave per row
 //        (2) per (b, slab): ds = a (da - a·da); dx[l,cols] = a_l du + ds_l w (1 - tanh^2 x); dw[cols] += sum_l ds_l tanh x
-constexpr int POOL_MAXL = 256;
+constexpr int POOL_MAXL = 512;     // slots per sample: each of the 256 threads of a slab block owns slots t and t + 256
 template <typename T>
 __global__ __launch_bounds__(256) void pool_score_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ out, const float* __restrict__ dout,
@@ -65,13 +65,17 @@ __global__ __launch_bounds__(256) void pool_out_kernel(const T* __restrict__ x, 
   __shared__ float part[4][4][64];
   typedef T quad __attribute__((ext_vector_type(4)));
   const int b = blockIdx.x, tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const float v = threadIdx.x < L ? score[(int64_t)b * L + threadIdx.x] : -INFINITY;
+  // softmax over the L scores, slots strided over the block (L <= 256: one slot per thread, the reductions see the same values)
+  float v = -INFINITY;
+  for (int l = threadIdx.x; l < L; l += 256) v = fmaxf(v, score[(int64_t)b * L + l]);
   const float m = block_max(v, red);
-  const float e = threadIdx.x < L ? __expf(v - m) : 0.f;
+  float e = 0.f;
+  for (int l = threadIdx.x; l < L; l += 256) e += __expf(score[(int64_t)b * L + l] - m);
   const float tot = block_sum(e, red);
-  if (threadIdx.x < L) {
-    a[threadIdx.x] = e / tot;
-    if (blockIdx.y == 0) attn[(int64_t)b * L + threadIdx.x] = e / tot;
+  for (int l = threadIdx.x; l < L; l += 256) {
+    const float al = __expf(score[(int64_t)b * L + l] - m) / tot;
+    a[l] = al;
+    if (blockIdx.y == 0) attn[(int64_t)b * L + l] = al;
   }
   __syncthreads();
   const int c = blockIdx.y * 256 + tx * 4;
@@ -91,7 +95,7 @@ __global__ __launch_bounds__(256) void pool_out_kernel(const T* __restrict__ x, 
   if (c < H) out[(int64_t)b * H + c + ty] = tanhf(sum);
 }
 
-template <typename T>
+template <typename T, bool WIDE>
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                        const float* __restrict__ attn, const float* __restrict__ out,
                                                        const float* __restrict__ dout, const float* __restrict__ da,
@@ -101,10 +105,21 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ x, 
   __shared__ float part[4][4][64];
   typedef T quad __attribute__((ext_vector_type(4)));
   const int b = blockIdx.x, tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const float a = threadIdx.x < L ? attn[(int64_t)b * L + threadIdx.x] : 0.f;
-  const float d = threadIdx.x < L ? da[(int64_t)b * L + threadIdx.x] : 0.f;
-  const float dot = block_sum(a * d, red);
-  if (threadIdx.x < L) { al[threadIdx.x] = a; ds[threadIdx.x] = a * (d - dot); }
+  if (!WIDE) {                     // L <= 256: one slot per thread; the product feeds the reduction directly (contracted into its first add)
+    const float a = threadIdx.x < L ? attn[(int64_t)b * L + threadIdx.x] : 0.f;
+    const float d = threadIdx.x < L ? da[(int64_t)b * L + threadIdx.x] : 0.f;
+    const float dot = block_sum(a * d, red);
+    if (threadIdx.x < L) { al[threadIdx.x] = a; ds[threadIdx.x] = a * (d - dot); }
+  } else {                         // slots strided over the block, as in pool_out_kernel
+    float ad = 0.f;
+    for (int l = threadIdx.x; l < L; l += 256) ad += attn[(int64_t)b * L + l] * da[(int64_t)b * L + l];
+    const float dot = block_sum(ad, red);
+    for (int l = threadIdx.x; l < L; l += 256) {
+      const float a = attn[(int64_t)b * L + l];
+      al[l] = a;
+      ds[l] = a * (da[(int64_t)b * L + l] - dot);
+    }
+  }
   __syncthreads();
   const int c = blockIdx.y * 256 + tx * 4;
   float dwp[4] = {0.f, 0.f, 0.f, 0.f};
@@ -623,10 +638,12 @@ extern "C" int goat_attn_pool_bwd(void* stream, int dtype, const void* x, const 
   dim3 g1((rows + 3) / 4), g2(B, (H + 255) / 256);
   if (dtype == GOAT_BF16) {
     hipLaunchKernelGGL(pool_score_kernel<bf16_t>, g1, dim3(256), 0, ST(stream), (const bf16_t*)x, w, out, dout, ws, rows, L, H);
-    hipLaunchKernelGGL(pool_bwd_kernel<bf16_t>, g2, dim3(256), 0, ST(stream), (const bf16_t*)x, w, attn, out, dout, ws, (bf16_t*)dx, dw, L, H);
+    if (L <= 256) hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, false>), g2, dim3(256), 0, ST(stream), (const bf16_t*)x, w, attn, out, dout, ws, (bf16_t*)dx, dw, L, H);
+    else hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, true>), g2, dim3(256), 0, ST(stream), (const bf16_t*)x, w, attn, out, dout, ws, (bf16_t*)dx, dw, L, H);
   } else if (dtype == GOAT_F32) {
     hipLaunchKernelGGL(pool_score_kernel<float>, g1, dim3(256), 0, ST(stream), (const float*)x, w, out, dout, ws, rows, L, H);
-    hipLaunchKernelGGL(pool_bwd_kernel<float>, g2, dim3(256), 0, ST(stream), (const float*)x, w, attn, out, dout, ws, (float*)dx, dw, L, H);
+    if (L <= 256) hipLaunchKernelGGL((pool_bwd_kernel<float, false>), g2, dim3(256), 0, ST(stream), (const float*)x, w, attn, out, dout, ws, (float*)dx, dw, L, H);
+    else hipLaunchKernelGGL((pool_bwd_kernel<float, true>), g2, dim3(256), 0, ST(stream), (const float*)x, w, attn, out, dout, ws, (float*)dx, dw, L, H);
   } else {
     return GOAT_E_ARG;
   }

@@ -977,6 +977,21 @@ def dropout(x, p):
 
 
 # ----------------------------------------------------------------------------- attention
+ATTN_SHORT_MAXLK = 256      # goat_attn_fwd / goat_attn_bwd (score row-block in registers; the tuned, captured path)
+ATTN_MAXLK = 512            # goat_attn_long_fwd / goat_attn_long_bwd (key-streaming forward)
+
+
+def _attn_entry(Lk):
+    """The pair of library entry points serving Lk keys: the long pair only above the short pair's limit, so nothing changes below it."""
+    if Lk > ATTN_MAXLK:
+        raise ValueError('attention over %d keys: the kernels serve at most %d (max_position_embeddings - 2 of the text encoder)'
+                         % (Lk, ATTN_MAXLK))
+    h = _lib.lib()
+    if Lk > ATTN_SHORT_MAXLK:
+        return h.goat_attn_long_fwd, h.goat_attn_long_bwd, 'goat_attn_long'
+    return h.goat_attn_fwd, h.goat_attn_bwd, 'goat_attn'
+
+
 class _AttnFn(torch.autograd.Function):
     """Masked MHA on packed projections.
     mode 'self' : a = qkv [B,L,3H]              (q|k|v)
@@ -1012,6 +1027,7 @@ class _AttnFn(torch.autograd.Function):
             k = (b, 0, ldb, Lk * ldb)
             v = (b, H, ldb, Lk * ldb)
         assert H == nh * 64, 'head_dim must be 64'
+        fwd, _, name = _attn_entry(Lk)
         o = torch.empty((B, Lq, H), dtype=a.dtype, device=a.device)
         lse = torch.empty((B, nh, Lq), dtype=torch.float32, device=a.device)
         if kmask is not None:
@@ -1020,13 +1036,13 @@ class _AttnFn(torch.autograd.Function):
             bias = bias.contiguous().float()
         seed, off, dev = RngState.next(B * nh * Lq * Lk) if p > 0 else (0, 0, None)
         scale = 1.0 / math.sqrt(64.0)
-        st = _lib.lib().goat_attn_fwd(
+        st = fwd(
             _stream(), _dt(a),
             _ptr(q[0], q[1]), q[2], q[3], _ptr(k[0], k[1]), k[2], k[3], _ptr(v[0], v[1]), v[2], v[3],
             _ptr(o), H, Lq * H,
             _ptr(kmask) if kmask is not None else None, _ptr(bias) if bias is not None else None, _ptr(lse),
             B, nh, Lq, Lk, scale, p, seed, off, dev)
-        _lib.check(st, 'goat_attn_fwd(Lq=%d,Lk=%d)' % (Lq, Lk))
+        _lib.check(st, '%s_fwd(Lq=%d,Lk=%d)' % (name, Lq, Lk))
         ctx.save_for_backward(a, b, kmask, bias, o, lse)
         ctx.cfg = (nh, p, seed, off, dev, scale)
         return o
@@ -1055,7 +1071,8 @@ class _AttnFn(torch.autograd.Function):
         dbias = None
         if bias is not None and ctx.needs_input_grad[3]:
             dbias = torch.zeros_like(bias)
-        st = _lib.lib().goat_attn_bwd(
+        _, bwd, name = _attn_entry(Lk)
+        st = bwd(
             _stream(), _dt(a),
             _ptr(q[0], q[1]), q[2], q[3], _ptr(k[0], k[1]), k[2], k[3], _ptr(v[0], v[1]), v[2], v[3],
             _ptr(o), H, Lq * H, _ptr(do), H, Lq * H,
@@ -1063,7 +1080,7 @@ class _AttnFn(torch.autograd.Function):
             _ptr(kmask) if kmask is not None else None, _ptr(bias) if bias is not None else None, _ptr(lse),
             _ptr(dbias) if dbias is not None else None,
             B, nh, Lq, Lk, scale, p, seed, off, dev)
-        _lib.check(st, 'goat_attn_bwd(Lq=%d,Lk=%d)' % (Lq, Lk))
+        _lib.check(st, '%s_bwd(Lq=%d,Lk=%d)' % (name, Lq, Lk))
         return da, db, None, dbias, None, None
 
 
