@@ -240,6 +240,40 @@ int goat_attn_long_bwd(void* stream, int dtype,
                        int B, int nh, int Lq, int Lk, float scale,
                        float p, uint64_t seed, uint64_t offset, const uint64_t* rng_dev);
 
+/* One step of KV-cached decoding (csrc/decode.hip): the speaker's word-by-word loop (M/r2r/transpeaker.py:292-322, which re-runs the
+ * decoder of M/models/transpeaker_model.py:200-230 over the whole prefix for every word) as a fixed-shape computation whose position
+ * lives in DEVICE memory, so that one captured hipGraph serves every step.
+ *
+ * goat_attn_decode_fwd: cache append + single-query attention, head_dim 64.  Let t = *pos_dev.  KVnew[b] (this step's K|V projection
+ * row, [B, 2*nh*64], dense) is copied into cache[b, t]; then
+ *   O[b,h,:] = dropout_p(softmax_{k<=t}(scale * Q[b,h,:]·K[b,k,h,:] + kmask[b,k])) · V[b,k,h,:]
+ * Q, O: [B, nh*64] dense.  cache: [B, Lmax, 2*nh*64] as K|V columns (K of head h at column h*64, V at nh*64 + h*64) with row stride
+ * c_rs and batch stride c_bs in elements.  kmask: float32 [B, Lmax] additive or NULL.  Keys k > t are never read: the cache tail (and
+ * the kmask tail) may hold anything, NaN included.  A row whose visible keys all carry -1e9 comes out uniform over the t+1 visible keys
+ * (the reference's masked_fill(-1e9) before the softmax, M/models/transpeaker_model.py:91-119); all -inf gives zeros.
+ * Dropout bits are a function of (seed + *rng_dev, offset, b, h, key) only (HeadRng of csrc/common.hpp), the same for both dtypes.
+ * 1 <= Lmax <= 512.  GOAT_E_SHAPE: Lmax outside that range, c_rs / c_bs not a multiple of the 16-byte chunk (4 f32 / 8 bf16 elements),
+ * c_rs < 2*nh*64, or a base pointer that is not 16-byte aligned.  GOAT_E_ARG: null Q / KVnew / cache / O / pos_dev, bad dtype, p outside
+ * [0, 1).  A t outside [0, Lmax) read on the device makes every workgroup return without touching memory. */
+int goat_attn_decode_fwd(void* stream, int dtype, const void* Q, const void* KVnew,
+                         void* cache, int64_t c_rs, int64_t c_bs, void* O,
+                         const float* kmask, const int32_t* pos_dev,
+                         int B, int nh, int Lmax, float scale,
+                         float p, uint64_t seed, uint64_t offset, const uint64_t* rng_dev);
+
+/* goat_decode_select: the next word of every row and the loop state in one launch — the logits[:, unk] = -inf, argmax / Categorical
+ * sample, pad-after-<EOS> and `ended` bookkeeping of M/r2r/transpeaker.py:303-322.  logits: float32 [B, ld], V <= ld valid columns.
+ * Let t = *pos_dev.  Per row: the column `unk` is never chosen; greedy (sampling == 0) takes the arg-max, a tie going to the LOWEST
+ * index (NaN counts as -inf); sampling != 0 draws from softmax(logits) by Gumbel-max over the counter hash of csrc/common.hpp, a
+ * function of (seed + *rng_dev, offset, b, column); a row with ended[b] != 0 gets `pad`.  The word goes to words[b, t+1]
+ * (int64 [B, Lmax]); kmask[b, t+1] (float32 [B, Lmax]) becomes -1e9 if the word is `pad`, else 0; a row that emits `eos` gets
+ * ended[b] = 1 and end_step[b] = t.  Then *pos_dev = t + 1 and *n_live = the number of rows not yet ended.  A t outside [0, Lmax - 1)
+ * read on the device: nothing is touched.  GOAT_E_ARG: a null pointer (rng_dev may be NULL); GOAT_E_SHAPE: V < 2, ld < V, Lmax < 2. */
+int goat_decode_select(void* stream, const float* logits, int64_t ld, int B, int V, int Lmax,
+                       int unk, int eos, int pad, int sampling,
+                       uint64_t seed, uint64_t offset, const uint64_t* rng_dev,
+                       int32_t* pos_dev, int64_t* words, float* kmask, uint8_t* ended, int32_t* end_step, int32_t* n_live);
+
 /* Softmax cross-entropy (reduction none) on float32 logits [M, ld] with N valid columns (ld >= N may be padded):
  * loss[m] = logsumexp(logits[m,:N]) - logits[m,target[m]], lse saved.  Replaces F.cross_entropy on the 576 x 50265
  * MLM scores (P/model/pretrain_goat.py:213-215).  Backward writes dlogits (GOAT_BF16 or GOAT_F32) with row stride

@@ -29,7 +29,9 @@ from ._plumbing import _dt, _epc, _need_gpu, _ptr, _stream          # noqa: E402
 
 class RngState:
     """Dropout counter state.  Eager: host counter.  Graph capture: `dev` (uint64 on device) is bumped
-    by one in-graph add per replay so every replay draws fresh masks (see goat_hip.h)."""
+    by one in-graph add per replay so every replay draws fresh masks (see goat_hip.h).  `dev` is process-wide: once set, EVERY op adds
+    its value to the seed, so whoever sets it owns the random streams of the process.  Code that needs a counter of its own for a graph
+    (speaker.IncrementalDecoder) installs it around its own ops only and puts the previous value back."""
     seed = None         # None: taken from torch.initial_seed() at first use (so torch.manual_seed / the reference trainer's
     rank_salt = 0       # set_random_seed(seed + rank) steer it); rank_salt: GoatDataParallel folds the rank in
     base = None         # what manual_seed() was given
@@ -1086,6 +1088,108 @@ class _AttnFn(torch.autograd.Function):
 
 def attention(a, b, kmask, bias, nh, p):
     return _AttnFn.apply(a, b, kmask, bias, int(nh), float(p))
+
+
+# ----------------------------------------------------------------------------- KV-cached decoding (inference only; csrc/decode.hip)
+DECODE_MAXL = 512           # goat_attn_decode_fwd: rows of a K|V cache
+
+
+def _inference_only(what, *tensors):
+    for t in tensors:
+        if t is not None and t.requires_grad:
+            raise RuntimeError('%s is inference-only (no backward pass): got a tensor that requires grad — call it under '
+                               'torch.no_grad() on detached tensors' % what)
+    for t in tensors:
+        if t is not None:
+            _need_gpu(t)
+
+
+class DecodeState:
+    """The loop state of a KV-cached decode, all in device memory at fixed addresses (goat_decode_select writes it, a captured step
+    reads it): words int64 [B, Lmax], kmask float32 [B, Lmax] (-1e9 where the word is <PAD>, else 0), ended uint8 [B],
+    end_step int32 [B] (the step at which the row emitted <EOS>, -1 before), pos int32 [1] (the column of the newest word),
+    n_live int32 [1] (rows not yet ended)."""
+
+    def __init__(self, B, Lmax, device):
+        if not 2 <= Lmax <= DECODE_MAXL:
+            raise ValueError('DecodeState: %d columns; the decode kernels serve 2..%d' % (Lmax, DECODE_MAXL))
+        self.B, self.Lmax = int(B), int(Lmax)
+        self.words = torch.zeros(B, Lmax, dtype=torch.int64, device=device)
+        self.kmask = torch.zeros(B, Lmax, dtype=torch.float32, device=device)
+        self.ended = torch.zeros(B, dtype=torch.uint8, device=device)
+        self.end_step = torch.full((B,), -1, dtype=torch.int32, device=device)
+        self.pos = torch.zeros(1, dtype=torch.int32, device=device)
+        self.n_live = torch.full((1,), B, dtype=torch.int32, device=device)
+
+    def reset(self, first, pad):
+        """Start a new batch of sentences: column 0 = `first` (an int or int64 [B]), everything else as after construction."""
+        self.words.fill_(pad)
+        self.words[:, 0] = first
+        self.kmask.zero_()
+        self.kmask[:, 0].masked_fill_(self.words[:, 0] == pad, -1e9)
+        self.ended.zero_()
+        self.end_step.fill_(-1)
+        self.pos.zero_()
+        self.n_live.fill_(self.B)
+
+
+def attn_decode(q, kv_new, cache, kmask, pos, nh, p=0.0):
+    """One KV-cached attention step (goat_attn_decode_fwd): with t = pos[0] ON THE DEVICE, cache[:, t] = kv_new and then single-query
+    attention of q over the keys 0..t.  q [B, nh*64] (or [B, 1, nh*64]); kv_new [B, 2*nh*64] (K|V); cache [B, Lmax, 2*nh*64] (updated in
+    place; the last dimension dense); kmask float32 [B, Lmax] additive or None; pos int32 [1].  -> o, shaped like q.  Inference only."""
+    _inference_only('attn_decode', q, kv_new, cache, kmask, pos)
+    H = int(nh) * 64
+    B, Lmax = cache.shape[0], cache.shape[1]
+    if q.numel() != B * H or kv_new.numel() != B * 2 * H or cache.dim() != 3 or cache.shape[2] != 2 * H:
+        raise ValueError('attn_decode: q %s / kv_new %s / cache %s do not fit %d heads of 64' % (tuple(q.shape), tuple(kv_new.shape), tuple(cache.shape), nh))
+    if not (q.dtype == kv_new.dtype == cache.dtype):
+        raise ValueError('attn_decode: q, kv_new and cache must share one dtype')
+    if cache.stride(2) != 1:
+        raise ValueError('attn_decode: the cache rows must be dense')
+    if pos.dtype != torch.int32 or pos.numel() != 1:
+        raise ValueError('attn_decode: pos is one int32 on the device')
+    if kmask is not None and (kmask.dtype != torch.float32 or tuple(kmask.shape) != (B, Lmax) or not kmask.is_contiguous()):
+        raise ValueError('attn_decode: kmask is a contiguous float32 [B, Lmax]')
+    for name, t in (('q', q), ('kv_new', kv_new), ('kmask', kmask), ('pos', pos)):
+        if t is not None and t.device != cache.device:
+            raise ValueError('attn_decode: %s is on %s, the cache on %s' % (name, t.device, cache.device))
+    qc = q if q.is_contiguous() else q.contiguous()
+    kvc = kv_new if kv_new.is_contiguous() else kv_new.contiguous()
+    o = torch.empty_like(qc)
+    p = float(p)
+    seed, off, dev = RngState.next(B * nh * Lmax) if p > 0 else (0, 0, None)
+    st = _lib.lib().goat_attn_decode_fwd(_stream(), _dt(qc), _ptr(qc), _ptr(kvc), _ptr(cache), cache.stride(1), cache.stride(0), _ptr(o),
+                                         _ptr(kmask) if kmask is not None else None, _ptr(pos), B, int(nh), Lmax,
+                                         1.0 / math.sqrt(64.0), p, seed, off, dev)
+    _lib.check(st, 'goat_attn_decode_fwd(B=%d,nh=%d,Lmax=%d)' % (B, nh, Lmax))
+    return o
+
+
+def decode_select(logits, state, unk, eos, pad, sampling=False, n_valid=None):
+    """The next word of every row and the loop state in one launch (goat_decode_select): with t = state.pos[0] on the device, row b's
+    word — arg-max of logits[b, :n_valid] without the column `unk` (ties: lowest index), or a categorical draw when `sampling`, or `pad`
+    if the row has ended — goes to state.words[b, t + 1]; kmask, ended, end_step, n_live follow and pos advances by one.
+    logits: float32 [B, ld] with n_valid <= ld valid columns (default: all).  Inference only."""
+    _inference_only('decode_select', logits, state.words)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError('decode_select: logits are float32 [B, ld] with dense rows')
+    B, ld = logits.shape
+    V = ld if n_valid is None else int(n_valid)
+    if B != state.B:
+        raise ValueError('decode_select: %d rows of logits for a state of %d' % (B, state.B))
+    if not 2 <= V <= ld:
+        raise ValueError('decode_select: %d valid columns of %d (at least 2, at most the row length)' % (V, ld))
+    want = (('words', torch.int64, (B, state.Lmax)), ('kmask', torch.float32, (B, state.Lmax)), ('ended', torch.uint8, (B,)),
+            ('end_step', torch.int32, (B,)), ('pos', torch.int32, (1,)), ('n_live', torch.int32, (1,)))
+    for name, dtype, shape in want:
+        t = getattr(state, name)
+        if t.device != logits.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError('decode_select: state.%s must be a contiguous %s %s on %s' % (name, dtype, list(shape), logits.device))
+    seed, off, dev = RngState.next(B * V) if sampling else (0, 0, None)
+    st = _lib.lib().goat_decode_select(_stream(), _ptr(logits), logits.stride(0), B, V, state.Lmax, int(unk), int(eos), int(pad),
+                                       1 if sampling else 0, seed, off, dev, _ptr(state.pos), _ptr(state.words), _ptr(state.kmask),
+                                       _ptr(state.ended), _ptr(state.end_step), _ptr(state.n_live))
+    _lib.check(st, 'goat_decode_select(B=%d,V=%d)' % (B, V))
 
 
 # ----------------------------------------------------------------------------- pano fusion / gather

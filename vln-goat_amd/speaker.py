@@ -244,6 +244,198 @@ def infer_batch(model, can_feats, img_feats, bos, eos, pad, unk, max_decode=120,
     return word
 
 
+# ------------------------------------------------------------------------------------------------ KV-cached, graph-replayed decoding
+def _proj_cat(x, weights):
+    """x @ cat(W_i)^T for bias-free Linears in one GEMM (the weights' concatenated shadow is cached and refreshed like every shadow)."""
+    x2 = x.reshape(-1, x.shape[-1])
+    if x2.shape[1] % 8 or not x2.is_contiguous():
+        return torch.cat([hipops.linear(x, w) for w in weights], -1)
+    W = hipops._shadow_cat(tuple(weights), x2.dtype)
+    out = torch.empty((x2.shape[0], W.shape[0]), dtype=x2.dtype, device=x2.device)
+    hipops.gemm(x2, W, out)
+    return out.view(*x.shape[:-1], W.shape[0])
+
+
+class IncrementalDecoder:
+    """`TranspeakerDecoder` + projection + word choice, one token per row and step, on static state — so that a step is a fixed-shape
+    computation: captured once (hipops.graph) after one eager warm-up step and replayed for every later word.
+
+    Static state: per layer the self-attention K|V cache [B, max_decode + 1, 2*nh*64] (compute dtype; goat_attn_decode_fwd appends
+    the step's row and attends over the rows written so far, the position read from device memory) and the cross-attention K|V of the
+    encoder output [B, ctx_len, 2*nh*64], projected ONCE per sentence batch by `start`; hipops.DecodeState (words, kmask, ended,
+    end_step, pos, n_live); the optional context bias [B, 1, ctx_len]; the float32 logits of the last step (`logits`).
+
+        dec = IncrementalDecoder(model, B, max_decode, T)
+        dec.start(enc_outputs, bos, pad, ctx_mask)             # new sentences
+        dec.step(unk, eos, pad, sampling)                      # x max_decode; words in dec.state.words[:, :pos + 1]
+        dec.force(next_words)                                  # (teacher forcing: replace the word the last step chose)
+
+    Honours what TranspeakerDecoder / MultiHeadAttention honour: `use_drop`, `attn_dropout_always`, the compute dtype (fixed at
+    construction), `ctx_mask`.  The step is a single-stream graph without parallel branches.
+
+    Random numbers.  A captured step bakes in the (seed, offset) pairs RngState.next handed out at capture, so what makes a replay draw
+    anew — dropout masks and, with `sampling`, the Gumbel noise of the word choice — is a device counter the step bumps itself.  The
+    decoder owns that counter (`rng_dev=`: an int64 [1] tensor of the caller's instead, e.g. to share one among decoders); it is
+    installed as hipops.RngState.dev only for the duration of a step and the process-wide value is put back afterwards, so decoding
+    leaves the random streams of every other op as they were.  Eager stepping (use_graph=False) bumps it too, on top of the host
+    offsets that advance anyway: eager and replayed steps are then different draws of the same distribution.
+
+    Against the prefix form (`infer_batch`): at p = 0 both compute the same function.  With attention dropout active
+    (`attn_dropout_always`, the reference's quirk) they are DIFFERENT RANDOM DRAWS of the same model: the prefix form re-draws the masks
+    of every position at every step, the cached form draws a position's masks once, when that position is decoded (and the `use_drop`
+    masks of the hoisted cross-attention K|V once per sentence batch)."""
+
+    def __init__(self, model, B, max_decode, ctx_len, use_graph=True, rng_dev=None):
+        dec = model.decoder
+        dev = model.projection.weight.device
+        self.model, self.B, self.max_decode, self.ctx_len = model, int(B), int(max_decode), int(ctx_len)
+        self.dtype = compute_dtype()
+        self.use_graph = use_graph
+        self.state = hipops.DecodeState(B, max_decode + 1, dev)
+        if rng_dev is not None and (rng_dev.dtype != torch.int64 or rng_dev.numel() != 1 or rng_dev.device != dev):
+            raise ValueError('rng_dev is one int64 on the device of the model')
+        self.rng_dev = rng_dev if rng_dev is not None else torch.zeros(1, dtype=torch.int64, device=dev)
+        self.self_kv, self.cross_kv = [], []
+        for layer in dec.layers:
+            Hs, Hc = layer.dec_self_attn.W_K.weight.shape[0], layer.dec_enc_attn.W_K.weight.shape[0]
+            self.self_kv.append(torch.zeros(B, max_decode + 1, 2 * Hs, dtype=self.dtype, device=dev))
+            self.cross_kv.append(torch.zeros(B, ctx_len, 2 * Hc, dtype=self.dtype, device=dev))
+        self.ctx_bias = torch.zeros(B, 1, ctx_len, dtype=torch.float32, device=dev)
+        self.has_ctx_mask = False
+        self.logits = torch.zeros(B, model.projection.weight.shape[0], dtype=torch.float32, device=dev)
+        self._graphs = {}           # (unk, eos, pad, sampling, ctx mask in use, dropout probabilities) -> captured step
+        self._warm = set()
+
+    @staticmethod
+    def _draws(probs):
+        return any(probs[i] > 0 for i in (0, 1, 2, 4, 5, 6))
+
+    # -- dropout probabilities at call time (they are baked into a captured step: part of the graph key)
+    def _probs(self):
+        m, d = self.model, self.model.decoder
+        at = d.layers[0].dec_self_attn
+        return (_p(d.drop) if d.use_drop else 0.0, _p(d.pos_emb.dropout), _p(at.dropout), bool(at.use_drop),
+                at.attn_p if at.attn_p is not None else _p(at.dropout), _p(d.layers[0].pos_ffn.fc[2]),
+                _p(m.dropout) if m.use_drop else 0.0)
+
+    @torch.no_grad()
+    def start(self, enc_outputs, first, pad=0, ctx_mask=None):
+        """New sentences: hoist the cross-attention K|V of enc_outputs [B, ctx_len, hidden], reset the loop state with `first`
+        (<BOS>, or int64 [B]) in column 0.  ctx_mask: bool [B, ctx_len] (True = padded context step) or None."""
+        if tuple(enc_outputs.shape[:2]) != (self.B, self.ctx_len):
+            raise ValueError('IncrementalDecoder built for [%d, %d] context steps, got %s' % (self.B, self.ctx_len, tuple(enc_outputs.shape[:2])))
+        enc = enc_outputs.detach().to(self.dtype)
+        for layer, kv in zip(self.model.decoder.layers, self.cross_kv):
+            at = layer.dec_enc_attn
+            x = _proj_cat(enc, (at.W_K.weight, at.W_V.weight))
+            if at.use_drop:
+                x = hipops.dropout(x, _p(at.dropout))
+            kv.copy_(x)
+        self.has_ctx_mask = ctx_mask is not None
+        self.ctx_bias.zero_()
+        if ctx_mask is not None:
+            self.ctx_bias.masked_fill_(ctx_mask.bool().unsqueeze(1), -1e9)
+        self.state.reset(first, pad)
+
+    def _attn_out(self, at, ctx, x):
+        out = at.ln(hipops.linear(ctx, at.fc.weight), x)
+        return hipops.dropout(out, _p(at.dropout))
+
+    def _step(self, unk, eos, pad, sampling):
+        m, dec, st = self.model, self.model.decoder, self.state
+        if sampling or self._draws(self._probs()):
+            self.rng_dev.add_(0x9E3779B1)                       # a replay draws new masks and new Gumbel noise
+        pos = st.pos.long()
+        ids = st.words.index_select(1, pos)                                                     # [B, 1]
+        x = hipops.embedding(ids, dec.embedding.weight, out_dtype=self.dtype, word_pad=dec.embedding.padding_idx)
+        if dec.use_drop:
+            x = hipops.dropout(x, _p(dec.drop))
+        x = x + dec.pos_emb.pe[:, 0].index_select(0, pos).to(self.dtype).unsqueeze(0)
+        x = hipops.dropout(x, _p(dec.pos_emb.dropout))
+        for layer, skv, ckv in zip(dec.layers, self.self_kv, self.cross_kv):
+            at = layer.dec_self_attn
+            q = hipops.linear(x, at.W_Q.weight)                                                 # [B, 1, H]
+            kv = _proj_cat(x, (at.W_K.weight, at.W_V.weight))                                   # [B, 1, 2H]: the row the cache gains
+            if at.use_drop:
+                q, kv = hipops.dropout(q, _p(at.dropout)), hipops.dropout(kv, _p(at.dropout))
+            p = at.attn_p if at.attn_p is not None else _p(at.dropout)
+            ctx = hipops.attn_decode(q, kv, skv, st.kmask, st.pos, at.n_heads, p)
+            x = self._attn_out(at, ctx, x)
+            at = layer.dec_enc_attn
+            q = hipops.linear(x, at.W_Q.weight)
+            if at.use_drop:
+                q = hipops.dropout(q, _p(at.dropout))
+            p = at.attn_p if at.attn_p is not None else _p(at.dropout)
+            ctx = hipops.attention(q, ckv, None, self.ctx_bias if self.has_ctx_mask else None, at.n_heads, p)
+            x = self._attn_out(at, ctx, x)
+            x = layer.pos_ffn(x)
+        if m.use_drop:
+            x = hipops.dropout(x, _p(m.dropout))
+        self.logits.copy_(hipops.linear(x, m.projection.weight, None, None, torch.float32)[:, 0])
+        hipops.decode_select(self.logits, st, unk, eos, pad, sampling)
+
+    @torch.no_grad()
+    def step(self, unk, eos, pad=0, sampling=False):
+        """Decode one word per row: state.words[:, pos + 1] is chosen and pos advances (on the device; nothing synchronises).  The first
+        step of a configuration runs eagerly (the warm-up: weight shadows, GEMM configurations), the second is captured, every later
+        one is a replay."""
+        if compute_dtype() != self.dtype:
+            raise RuntimeError('IncrementalDecoder was built for %s; the compute dtype is now %s' % (self.dtype, compute_dtype()))
+        probs = self._probs()
+        key = (int(unk), int(eos), int(pad), bool(sampling), self.has_ctx_mask, probs)
+        g = self._graphs.get(key)
+        if g is None:
+            outer, hipops.RngState.dev = hipops.RngState.dev, self.rng_dev      # (the ops of the step take the counter's address from here)
+            try:
+                if not self.use_graph or key not in self._warm:
+                    self._warm.add(key)
+                    return self._step(unk, eos, pad, sampling)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with hipops.graph(g):
+                    self._step(unk, eos, pad, sampling)
+                self._graphs[key] = g
+            finally:
+                hipops.RngState.dev = outer
+        g.replay()
+
+    @torch.no_grad()
+    def force(self, next_words, pad=0):
+        """Teacher forcing: replace the word the last step chose (column pos) by next_words int64 [B]; its key mask follows."""
+        pos = self.state.pos.long()
+        w = next_words.to(torch.int64).reshape(self.B, 1)
+        self.state.words.index_copy_(1, pos, w)
+        self.state.kmask.index_copy_(1, pos, torch.zeros_like(w, dtype=torch.float32).masked_fill_(w == pad, -1e9))
+
+
+@torch.no_grad()
+def infer_batch_cached(model, can_feats, img_feats, bos, eos, pad, unk, max_decode=120, sampling=False, already_dropfeat=False,
+                       ctx_mask=None, check_every=8, decoder=None):
+    """`infer_batch` with a KV cache and a captured step (IncrementalDecoder): encode once, hoist the cross-attention K|V once, then
+    one graph replay per word; the only device-to-host reads are n_live once every `check_every` steps and end_step at the end.
+    Same result contract: int64 [B, <= max_decode + 1] including <BOS>, cut where the last row ended (1 + max(end_step) + 1 columns),
+    <UNK> never produced, finished rows padded.  decoder=: reuse one IncrementalDecoder (and its captured graph) across batches of the
+    same B, max_decode and context length.
+
+    At p = 0 this is the function `infer_batch` computes.  With attention dropout active (`attn_dropout_always`, the reference's quirk)
+    the two are different random draws: the prefix form re-draws every position's masks at every step, this form draws a position's
+    masks once, when that position is decoded."""
+    enc_inputs, enc_outputs = model.encoder(can_feats, img_feats, already_dropfeat)
+    B, T = enc_outputs.shape[0], enc_outputs.shape[1]
+    dec = decoder if decoder is not None else IncrementalDecoder(model, B, max_decode, T)
+    if (dec.B, dec.max_decode, dec.ctx_len) != (B, max_decode, T) or dec.model is not model:
+        raise ValueError('decoder= was built for another model or (B, max_decode, ctx_len) = (%d, %d, %d)' % (dec.B, dec.max_decode, dec.ctx_len))
+    dec.start(enc_outputs, bos, pad, ctx_mask)
+    check_every = max(1, int(check_every))
+    for s in range(max_decode):
+        dec.step(unk, eos, pad, sampling)
+        if (s + 1) % check_every == 0 and s + 1 < max_decode and int(dec.state.n_live.item()) == 0:
+            break
+    st = dec.state
+    n = max_decode + 1 if int(st.n_live.item()) else int(st.end_step.max().item()) + 2
+    return st.words[:, :n].clone()
+
+
 def path_features(sim, store, episodes, angle_size=128):
     """`from_shortest_path` (M/r2r/transpeaker.py:158-199) on the graph-only navigator: walk every ground-truth path; per step the
     36 view features + their relative angle features (`speaker_feature` of the observation, M/r2r/env.py:362-364) and the feature of
