@@ -5,6 +5,7 @@ The product path has NO fallback: if the library is missing or a call fails, a R
 re-uses the copy PyTorch already loaded, so HIP streams and device pointers are shared with torch.
 """
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -110,7 +111,7 @@ def build(force=False, verbose=False):
     """Compile csrc/*.hip for gfx950 into csrc/libgoat_hip.so (in-tree, travels with the repo snapshot)."""
     force = force or os.environ.get('GOAT_FORCE_BUILD', '0') == '1'
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'gemm2_tile.hpp'), os.path.join(CSRC, 'gemm5_tile.hpp'), os.path.join(CSRC, 'gemm_epilogue.hpp'), os.path.join(CSRC, 'gemm_args.hpp'), os.path.join(CSRC, 'attn_args.hpp'), os.path.join(CSRC, 'attn_tile.hpp'), os.path.join(_HERE, '..', 'include', 'goat_hip.h')]
+    deps = srcs + glob.glob(os.path.join(CSRC, '*.hpp')) + [os.path.join(_HERE, '..', 'include', 'goat_hip.h')]      # every header: one missing from a hand-kept list means a stale library that still loads
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         LAST_BUILD[0] = 'reused (library newer than every source; GOAT_FORCE_BUILD=1 or build(force=True) recompiles)'
         return LIB_PATH

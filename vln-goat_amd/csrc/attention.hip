@@ -347,13 +347,7 @@ template <typename T>
 int launch_bwd2(hipStream_t st, const AttnArgs& a) {
   const int nkt = (a.Lk + 31) / 32, nqt = (a.Lq + 31) / 32;
   const size_t sm = (size_t)nkt * 32 * AT<T>::LSTR * sizeof(T);
-  static size_t attr = 0;
-  if (sm > 64 * 1024 && sm > attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_kernel<T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    if (e != hipSuccess) return (int)e;
-    attr = sm;
-  }
+  if (int e = set_smem<attn_bwd_dq_kernel<T>>(sm)) return e;
   hipLaunchKernelGGL(attn_bwd_dq_kernel<T>, dim3(a.B * a.nh, nqt), dim3(64), sm, st, a);
   GOAT_LAUNCH_CHECK();
   hipLaunchKernelGGL(attn_bwd_dkv_kernel<T>, dim3(a.B * a.nh, nkt), dim3(64), 0, st, a);
@@ -364,24 +358,13 @@ int launch_bwd2(hipStream_t st, const AttnArgs& a) {
 template <typename T>
 size_t fwd_smem(int nkt) { return (size_t)nkt * 32 * AT<T>::LSTR * sizeof(T); }
 
-template <typename K>
-int set_smem(K kern, size_t bytes) {
-  if (bytes > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)bytes);
-    if (e != hipSuccess) return (int)e;
-  }
-  return 0;
-}
-
 template <typename T, int NKT>
 int launch_fwd(hipStream_t st, const AttnArgs& a) {
   const int nqt = (a.Lq + 31) / 32;
   const int wpb = nqt < 8 ? nqt : 8;  // waves per block
   dim3 grid(a.B * a.nh, (nqt + wpb - 1) / wpb);
   size_t sm = fwd_smem<T>(NKT);
-  int e = set_smem(attn_fwd_kernel<T, NKT>, sm);
-  if (e) return e;
+  if (int e = set_smem<attn_fwd_kernel<T, NKT>>(sm)) return e;
   hipLaunchKernelGGL((attn_fwd_kernel<T, NKT>), grid, dim3(64 * wpb), sm, st, a);
   GOAT_LAUNCH_CHECK();
   return 0;
@@ -407,7 +390,7 @@ bool use_v2() {       // GOAT_ATTN_V1=1: the round-1 kernels for every problem (
 }  // namespace
 
 int goat_attn_tile_bwd(hipStream_t st, const AttnArgs& a, int dtype) {
-  return dtype == GOAT_BF16 ? launch_bwd2<bf16_t>(st, a) : launch_bwd2<float>(st, a);
+  return dtype_dispatch(dtype, [&](auto dt) -> int { return launch_bwd2<GOAT_DT_TYPE(dt)>(st, a); });
 }
 
 extern "C" int goat_attn_fwd(void* stream, int dtype, const void* Q, int64_t q_rs, int64_t q_bs, const void* K,
@@ -415,22 +398,15 @@ extern "C" int goat_attn_fwd(void* stream, int dtype, const void* Q, int64_t q_r
                              int64_t o_rs, int64_t o_bs, const float* kmask, const float* bias, float* lse, int B,
                              int nh, int Lq, int Lk, float scale, float p, uint64_t seed, uint64_t offset,
                              const uint64_t* rng_dev) {
-  if (!Q || !K || !V || !O || !lse) return GOAT_E_ARG;
-  if (B <= 0 || nh <= 0 || Lq <= 0 || Lk <= 0 || Lk > 256) return GOAT_E_SHAPE;
-  if (dtype != GOAT_F32 && dtype != GOAT_BF16) return GOAT_E_ARG;
-  if (!strides_ok(dtype, q_rs, q_bs, Q) || !strides_ok(dtype, k_rs, k_bs, K) || !strides_ok(dtype, v_rs, v_bs, V))
-    return GOAT_E_SHAPE;
-  AttnArgs a = {};
-  a.Q = Q; a.K = K; a.V = V; a.Ow = O;
-  a.q_rs = q_rs; a.q_bs = q_bs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.o_rs = o_rs; a.o_bs = o_bs;
-  a.kmask = kmask; a.bias = bias; a.lse = lse;
-  a.B = B; a.nh = nh; a.Lq = Lq; a.Lk = Lk; a.scale = scale; a.p = p; a.seed = seed; a.offset = offset; a.rng_dev = rng_dev;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == GOAT_BF16 && use_v2()) {          // LDS-staged kernels (attention2.hip) for Lq, Lk <= 128
-    const int rc = goat_attn2_fwd(st, a);
+  AttnArgs a;
+  if (int e = attn_fwd_args(a, 256, false, dtype, Q, q_rs, q_bs, K, k_rs, k_bs, V, v_rs, v_bs, O, o_rs, o_bs, kmask, bias, lse, B, nh, Lq,
+                            Lk, scale, p, seed, offset, rng_dev))
+    return e;
+  if (dtype == GOAT_BF16 && use_v2()) {          // LDS-staged kernels (attention2.hip) first: GOAT_E_SHAPE means "not theirs"
+    const int rc = goat_attn2_fwd(ST(stream), a);
     if (rc != GOAT_E_SHAPE) return rc;
   }
-  return dtype == GOAT_BF16 ? dispatch_fwd<bf16_t>(st, a) : dispatch_fwd<float>(st, a);
+  return dtype_dispatch(dtype, [&](auto dt) -> int { return dispatch_fwd<GOAT_DT_TYPE(dt)>(ST(stream), a); });
 }
 
 extern "C" int goat_attn_bwd(void* stream, int dtype, const void* Q, int64_t q_rs, int64_t q_bs, const void* K,
@@ -440,23 +416,13 @@ extern "C" int goat_attn_bwd(void* stream, int dtype, const void* Q, int64_t q_r
                              int64_t dv_rs, int64_t dv_bs, const float* kmask, const float* bias, const float* lse,
                              float* dbias, int B, int nh, int Lq, int Lk, float scale, float p, uint64_t seed,
                              uint64_t offset, const uint64_t* rng_dev) {
-  if (!Q || !K || !V || !O || !dO || !dQ || !dK || !dV || !lse) return GOAT_E_ARG;
-  if (B <= 0 || nh <= 0 || Lq <= 0 || Lk <= 0 || Lk > 256) return GOAT_E_SHAPE;
-  if (dtype != GOAT_F32 && dtype != GOAT_BF16) return GOAT_E_ARG;
-  if (!strides_ok(dtype, q_rs, q_bs, Q) || !strides_ok(dtype, k_rs, k_bs, K) || !strides_ok(dtype, v_rs, v_bs, V) ||
-      !strides_ok(dtype, o_rs, o_bs, O) || !strides_ok(dtype, do_rs, do_bs, dO) || !strides_ok(dtype, dq_rs, dq_bs, dQ))
-    return GOAT_E_SHAPE;
-  AttnArgs a = {};
-  a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.dQ = dQ; a.dK = dK; a.dV = dV;
-  a.q_rs = q_rs; a.q_bs = q_bs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.o_rs = o_rs; a.o_bs = o_bs;
-  a.do_rs = do_rs; a.do_bs = do_bs; a.dq_rs = dq_rs; a.dq_bs = dq_bs; a.dk_rs = dk_rs; a.dk_bs = dk_bs;
-  a.dv_rs = dv_rs; a.dv_bs = dv_bs;
-  a.kmask = kmask; a.bias = bias; a.lse = const_cast<float*>(lse); a.dbias = dbias;
-  a.B = B; a.nh = nh; a.Lq = Lq; a.Lk = Lk; a.scale = scale; a.p = p; a.seed = seed; a.offset = offset; a.rng_dev = rng_dev;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  AttnArgs a;
+  if (int e = attn_bwd_args(a, 256, dtype, Q, q_rs, q_bs, K, k_rs, k_bs, V, v_rs, v_bs, O, o_rs, o_bs, dO, do_rs, do_bs, dQ, dq_rs, dq_bs,
+                            dK, dk_rs, dk_bs, dV, dv_rs, dv_bs, kmask, bias, lse, dbias, B, nh, Lq, Lk, scale, p, seed, offset, rng_dev))
+    return e;
   if (dtype == GOAT_BF16 && use_v2()) {
-    const int rc = goat_attn2_bwd(st, a);
+    const int rc = goat_attn2_bwd(ST(stream), a);
     if (rc != GOAT_E_SHAPE) return rc;
   }
-  return dtype == GOAT_BF16 ? launch_bwd2<bf16_t>(st, a) : launch_bwd2<float>(st, a);
+  return goat_attn_tile_bwd(ST(stream), a, dtype);
 }

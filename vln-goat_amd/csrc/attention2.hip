@@ -13,12 +13,12 @@
 //             role (cheaper than a cross-wave reduction); D = rowsum(dO * O) is computed while dO is staged.
 // Semantics (additive key mask, optional [B,Lq,Lk] bias with gradient, dropout on the probabilities from the stateless
 // counter hash, LSE saved) are exactly those of attention.hip; P/model/Bert_backbone.py:246-290, transformer.py:172-176.
-#include "attn_args.hpp"
+#include "attn_tile.hpp"
 
 namespace {
 
-constexpr int HD = 64, NE = 8, LSTR = HD + NE;     // LDS row stride in elements (144 B: conflict-free 16-byte fragment reads)
-constexpr int KSTEPS = 4, TSTEPS = 2;
+constexpr int NE = AT<bf16_t>::NE, LSTR = AT<bf16_t>::LSTR;     // LDS row stride in elements (144 B: conflict-free 16-byte fragment reads)
+constexpr int KSTEPS = AT<bf16_t>::KSTEPS, TSTEPS = AT<bf16_t>::TSTEPS;
 constexpr int TILE = 32 * LSTR;                      // elements per 32-row tile
 #ifndef GOAT_ATTN_TIMING     // experiments only: forward kernel writes 8 s_memtime stamps of wave 0 per block behind the LSE array (the caller allocates B*nh*8 extra words)
 #define GOAT_ATTN_TIMING 0
@@ -32,25 +32,7 @@ constexpr int TILE = 32 * LSTR;                      // elements per 32-row tile
 __device__ __forceinline__ bf16x8 lds_frag(const bf16_t* tile, int row, int ks, int hi) {
   return *reinterpret_cast<const bf16x8*>(tile + row * LSTR + (ks * 2 + hi) * NE);
 }
-// B fragment "fixed column, accumulator-pattern rows" of a row-major [row][64] LDS tile: two ds_read_b64_tr_b16
-__device__ __forceinline__ bf16x8 bfrag_crow(const bf16_t* lds, int row_base, int step, int dt, int lane) {
-  typedef __attribute__((address_space(3))) bf16x4 lds_b4;
-  const int g = lane >> 4, t15 = lane & 15;
-  const int col = dt * 32 + (g & 1) * 16 + (t15 & 3) * 4;
-  const int r0 = row_base + 16 * step + 4 * (g >> 1) + (t15 >> 2);
-  bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(lds + r0 * LSTR + col));
-  bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_b4*)(lds + (r0 + 8) * LSTR + col));
-  bf16x8 f;
-  f[0] = v0[0]; f[1] = v0[1]; f[2] = v0[2]; f[3] = v0[3];
-  f[4] = v1[0]; f[5] = v1[1]; f[6] = v1[2]; f[7] = v1[3];
-  return f;
-}
-__device__ __forceinline__ bf16x8 acc_frag(const f32x16& a, int step) {
-  bf16x8 f;
-#pragma unroll
-  for (int e = 0; e < NE; ++e) f[e] = (bf16_t)a[step * NE + e];
-  return f;
-}
+// (bfrag_crow<bf16_t> and acc_frag<bf16_t> come from attn_tile.hpp; every tile here has the row stride LSTR)
 // One operand of a (sample, head): [nrows, 64] head slice in global memory (row stride rs) -> LDS [rows_pad][LSTR], zero beyond nrows
 struct StageOp {
   const bf16_t* g;
@@ -293,9 +275,9 @@ __global__ __launch_bounds__(256) void attn2_fwd_kernel(AttnArgs p) {
   for (int jt = 0; jt < NKT; ++jt)
 #pragma unroll
     for (int st = 0; st < TSTEPS; ++st) {
-      const bf16x8 pa = acc_frag(s[jt], st);
+      const bf16x8 pa = acc_frag<bf16_t>(s[jt], st);
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt) mma32(o[dt], bfrag_crow(vl, jt * 32, st, dt, lane), pa);
+      for (int dt = 0; dt < 2; ++dt) mma32(o[dt], bfrag_crow<bf16_t>(vl, LSTR, jt * 32, st, dt, lane), pa);
     }
   GOAT_STAMP(6);
   store_tile(qt, o, Ob, p.o_rs, q0, p.Lq, lane);          // this query tile's Q rows are dead: nobody else reads them
@@ -439,9 +421,9 @@ __global__ __launch_bounds__(512) void attn2_bwd_kernel(AttnArgs p) {
       }
 #pragma unroll
       for (int st = 0; st < TSTEPS; ++st) {
-        const bf16x8 a = acc_frag(ds, st);
+        const bf16x8 a = acc_frag<bf16_t>(ds, st);
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) mma32(ra[dt], bfrag_crow(kl, jt * 32, st, dt, lane), a);
+        for (int dt = 0; dt < 2; ++dt) mma32(ra[dt], bfrag_crow<bf16_t>(kl, LSTR, jt * 32, st, dt, lane), a);
       }
     }
   } else {
@@ -491,11 +473,11 @@ __global__ __launch_bounds__(512) void attn2_bwd_kernel(AttnArgs p) {
       }
 #pragma unroll
       for (int st = 0; st < TSTEPS; ++st) {
-        const bf16x8 ap = acc_frag(pd, st), as = acc_frag(ds, st);
+        const bf16x8 ap = acc_frag<bf16_t>(pd, st), as = acc_frag<bf16_t>(ds, st);
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          mma32(rb[dt], bfrag_crow(dol, q0, st, dt, lane), ap);
-          mma32(ra[dt], bfrag_crow(ql, q0, st, dt, lane), as);
+          mma32(rb[dt], bfrag_crow<bf16_t>(dol, LSTR, q0, st, dt, lane), ap);
+          mma32(ra[dt], bfrag_crow<bf16_t>(ql, LSTR, q0, st, dt, lane), as);
         }
       }
     }
@@ -772,8 +754,8 @@ __global__ __launch_bounds__(512) void attn2_bwd_shared_kernel(AttnArgs p) {
       for (int st = 0; st < TSTEPS; ++st) {
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-          mma32(rb[dt], bfrag_crow(dol, q0, st, dt, lane), apf[st]);
-          mma32(ra[dt], bfrag_crow(ql, q0, st, dt, lane), asf[st]);
+          mma32(rb[dt], bfrag_crow<bf16_t>(dol, LSTR, q0, st, dt, lane), apf[st]);
+          mma32(ra[dt], bfrag_crow<bf16_t>(ql, LSTR, q0, st, dt, lane), asf[st]);
         }
       }
     }
@@ -812,22 +794,11 @@ __global__ __launch_bounds__(512) void attn2_bwd_shared_kernel(AttnArgs p) {
 #undef GOAT_DVB
 }
 
-template <typename K>
-int set_smem(K kern, size_t bytes, size_t& cur) {
-  if (bytes > 64 * 1024 && bytes > cur) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return (int)e;
-    cur = bytes;
-  }
-  return 0;
-}
-
 template <int NKT>
 int launch_fwd(hipStream_t st, const AttnArgs& a) {
   const int nqt = (a.Lq + 31) / 32;
   const size_t sm = (size_t)(2 * NKT + nqt) * TILE * 2 + NKT * 32 * 4;
-  static size_t cur = 0;
-  if (int e = set_smem(attn2_fwd_kernel<NKT>, sm, cur)) return e;
+  if (int e = set_smem<attn2_fwd_kernel<NKT>>(sm)) return e;
   if (sm > 160 * 1024) return GOAT_E_SHAPE;
   hipLaunchKernelGGL(attn2_fwd_kernel<NKT>, dim3(a.B * a.nh), dim3(64 * (nqt < 2 ? 2 : (nqt < 4 ? nqt : 4))), sm, st, a);   // (one query tile: a second wave helps staging K / V)
   GOAT_LAUNCH_CHECK();
@@ -874,8 +845,7 @@ int goat_attn2_bwd(hipStream_t st, const AttnArgs& a) {
       const dim3 grid(a.B * a.nh), block(64 * (nkt > 2 ? nkt : 2));
 #define GOAT_BWD_LAUNCH(DSS_, D_, E_)                                                                   \
   do {                                                                                                  \
-    static size_t cur_s = 0;                                                                            \
-    if (int e = set_smem(attn2_bwd_shared_kernel<DSS_, D_, E_>, sms, cur_s)) return e;                  \
+    if (int e = set_smem<attn2_bwd_shared_kernel<DSS_, D_, E_>>(sms)) return e;                         \
     hipLaunchKernelGGL((attn2_bwd_shared_kernel<DSS_, D_, E_>), grid, block, sms, st, a);               \
   } while (0)
 #define GOAT_BWD_DE(DSS_)                                                                               \
@@ -906,12 +876,11 @@ int goat_attn2_bwd(hipStream_t st, const AttnArgs& a) {
     sm = sm0 + (size_t)nwv * TILE * 2;
   }
   if (sm > 160 * 1024) return GOAT_E_SHAPE;          // (e.g. 256 x 256: the caller falls back to the streaming kernels of attention.hip)
-  static size_t cur = 0, cur_m = 0;
   if (nqt + nkt > 8) {
-    if (int e = set_smem(attn2_bwd_kernel<true>, sm, cur_m)) return e;
+    if (int e = set_smem<attn2_bwd_kernel<true>>(sm)) return e;
     hipLaunchKernelGGL(attn2_bwd_kernel<true>, dim3(a.B * a.nh), dim3(64 * nwv), sm, st, a);
   } else {
-    if (int e = set_smem(attn2_bwd_kernel<false>, sm, cur)) return e;
+    if (int e = set_smem<attn2_bwd_kernel<false>>(sm)) return e;
     hipLaunchKernelGGL(attn2_bwd_kernel<false>, dim3(a.B * a.nh), dim3(64 * nwv), sm, st, a);
   }
   GOAT_LAUNCH_CHECK();

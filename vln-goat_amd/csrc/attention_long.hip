@@ -193,19 +193,11 @@ extern "C" int goat_attn_long_fwd(void* stream, int dtype, const void* Q, int64_
                                   int64_t o_rs, int64_t o_bs, const float* kmask, const float* bias, float* lse, int B,
                                   int nh, int Lq, int Lk, float scale, float p, uint64_t seed, uint64_t offset,
                                   const uint64_t* rng_dev) {
-  if (!Q || !K || !V || !O || !lse) return GOAT_E_ARG;
-  if (B <= 0 || nh <= 0 || Lq <= 0 || Lk <= 0 || Lk > LONG_MAXLK) return GOAT_E_SHAPE;
-  if (dtype != GOAT_F32 && dtype != GOAT_BF16) return GOAT_E_ARG;
-  if (!strides_ok(dtype, q_rs, q_bs, Q) || !strides_ok(dtype, k_rs, k_bs, K) || !strides_ok(dtype, v_rs, v_bs, V) ||
-      !strides_ok(dtype, o_rs, o_bs, O))
-    return GOAT_E_SHAPE;
-  AttnArgs a = {};
-  a.Q = Q; a.K = K; a.V = V; a.Ow = O;
-  a.q_rs = q_rs; a.q_bs = q_bs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.o_rs = o_rs; a.o_bs = o_bs;
-  a.kmask = kmask; a.bias = bias; a.lse = lse;
-  a.B = B; a.nh = nh; a.Lq = Lq; a.Lk = Lk; a.scale = scale; a.p = p; a.seed = seed; a.offset = offset; a.rng_dev = rng_dev;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  return dtype == GOAT_BF16 ? launch_long_fwd<bf16_t>(st, a) : launch_long_fwd<float>(st, a);
+  AttnArgs a;
+  if (int e = attn_fwd_args(a, LONG_MAXLK, true, dtype, Q, q_rs, q_bs, K, k_rs, k_bs, V, v_rs, v_bs, O, o_rs, o_bs, kmask, bias, lse, B,
+                            nh, Lq, Lk, scale, p, seed, offset, rng_dev))
+    return e;
+  return dtype_dispatch(dtype, [&](auto dt) -> int { return launch_long_fwd<GOAT_DT_TYPE(dt)>(ST(stream), a); });
 }
 
 extern "C" int goat_attn_long_bwd(void* stream, int dtype, const void* Q, int64_t q_rs, int64_t q_bs, const void* K,
@@ -215,18 +207,10 @@ extern "C" int goat_attn_long_bwd(void* stream, int dtype, const void* Q, int64_
                                   int64_t dv_rs, int64_t dv_bs, const float* kmask, const float* bias, const float* lse,
                                   float* dbias, int B, int nh, int Lq, int Lk, float scale, float p, uint64_t seed,
                                   uint64_t offset, const uint64_t* rng_dev) {
-  if (!Q || !K || !V || !O || !dO || !dQ || !dK || !dV || !lse) return GOAT_E_ARG;
-  if (B <= 0 || nh <= 0 || Lq <= 0 || Lk <= 0 || Lk > LONG_MAXLK) return GOAT_E_SHAPE;
-  if (dtype != GOAT_F32 && dtype != GOAT_BF16) return GOAT_E_ARG;
-  if (!strides_ok(dtype, q_rs, q_bs, Q) || !strides_ok(dtype, k_rs, k_bs, K) || !strides_ok(dtype, v_rs, v_bs, V) ||
-      !strides_ok(dtype, o_rs, o_bs, O) || !strides_ok(dtype, do_rs, do_bs, dO) || !strides_ok(dtype, dq_rs, dq_bs, dQ))
-    return GOAT_E_SHAPE;
-  AttnArgs a = {};
-  a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.dQ = dQ; a.dK = dK; a.dV = dV;
-  a.q_rs = q_rs; a.q_bs = q_bs; a.k_rs = k_rs; a.k_bs = k_bs; a.v_rs = v_rs; a.v_bs = v_bs; a.o_rs = o_rs; a.o_bs = o_bs;
-  a.do_rs = do_rs; a.do_bs = do_bs; a.dq_rs = dq_rs; a.dq_bs = dq_bs; a.dk_rs = dk_rs; a.dk_bs = dk_bs;
-  a.dv_rs = dv_rs; a.dv_bs = dv_bs;
-  a.kmask = kmask; a.bias = bias; a.lse = const_cast<float*>(lse); a.dbias = dbias;
-  a.B = B; a.nh = nh; a.Lq = Lq; a.Lk = Lk; a.scale = scale; a.p = p; a.seed = seed; a.offset = offset; a.rng_dev = rng_dev;
-  return goat_attn_tile_bwd(reinterpret_cast<hipStream_t>(stream), a, dtype);
+  AttnArgs a;
+  if (int e = attn_bwd_args(a, LONG_MAXLK, dtype, Q, q_rs, q_bs, K, k_rs, k_bs, V, v_rs, v_bs, O, o_rs, o_bs, dO, do_rs, do_bs, dQ, dq_rs,
+                            dq_bs, dK, dk_rs, dk_bs, dV, dv_rs, dv_bs, kmask, bias, lse, dbias, B, nh, Lq, Lk, scale, p, seed, offset,
+                            rng_dev))
+    return e;
+  return goat_attn_tile_bwd(ST(stream), a, dtype);
 }

@@ -1,6 +1,8 @@
-// Tile helpers shared by the one-wave-per-tile attention kernels (attention.hip: Lk <= 256, whole score row-block in accumulators;
-// attention_long.hip: key-streaming forward for Lk <= 512): fragment loads / gathers for MFMA 32x32 tiles of 64-wide head rows, the
-// row staging copy, the dropout decision both families (and attention2.hip's HeadRng for bf16) share, and the stride rule.
+// Device-side tile helpers shared by the three attention families (attention.hip: one wave per tile, Lk <= 256, whole score row-block
+// in accumulators; attention_long.hip: key-streaming forward for Lk <= 512; attention2.hip: the LDS-staged bf16 kernels): the tile
+// constants AT<T>, fragment loads / gathers for MFMA 32x32 tiles of 64-wide head rows (bfrag_crow, acc_frag: all three families),
+// and, for the two one-wave-per-tile families, the row staging copy and the dropout decision AttnMask (which draws attention2.hip's
+// HeadRng bits for bf16).  The argument block, its builders and the other host helpers are in attn_args.hpp.
 #pragma once
 #include "attn_args.hpp"
 
@@ -113,10 +115,5 @@ struct AttnMask {
     return g.keep(base + (uint64_t)q * (uint64_t)p.Lk + key, thr);
   }
 };
-
-bool strides_ok(int dtype, int64_t rs, int64_t bs, const void* ptr) {
-  const int epc = dtype == GOAT_BF16 ? 8 : 4;
-  return (rs % epc) == 0 && (bs % epc) == 0 && (reinterpret_cast<uintptr_t>(ptr) & 15) == 0;
-}
 
 }  // namespace

@@ -7,23 +7,6 @@
 
 namespace {
 
-__device__ __forceinline__ float block_sum(float v, float* red) {   // 256 threads
-  v = wave_sum(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
 // ------------------------------------------------------------------------------------ tanh-attention pooling
 // a = softmax_l(tanh(x_l)·w) over ALL L slots (no padding mask, as the reference); out = tanh(sum_l a_l x_l)
 // Two launches per direction so that B*L rows / B*H/256 column slabs (not just B samples) are in flight:
@@ -68,10 +51,10 @@ __global__ __launch_bounds__(256) void pool_out_kernel(const T* __restrict__ x, 
   // softmax over the L scores, slots strided over the block (L <= 256: one slot per thread, the reductions see the same values)
   float v = -INFINITY;
   for (int l = threadIdx.x; l < L; l += 256) v = fmaxf(v, score[(int64_t)b * L + l]);
-  const float m = block_max(v, red);
+  const float m = block_reduce<true, 4>(v, red);
   float e = 0.f;
   for (int l = threadIdx.x; l < L; l += 256) e += __expf(score[(int64_t)b * L + l] - m);
-  const float tot = block_sum(e, red);
+  const float tot = block_reduce<false, 4>(e, red);
   for (int l = threadIdx.x; l < L; l += 256) {
     const float al = __expf(score[(int64_t)b * L + l] - m) / tot;
     a[l] = al;
@@ -108,12 +91,12 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const T* __restrict__ x, 
   if (!WIDE) {                     // L <= 256: one slot per thread; the product feeds the reduction directly (contracted into its first add)
     const float a = threadIdx.x < L ? attn[(int64_t)b * L + threadIdx.x] : 0.f;
     const float d = threadIdx.x < L ? da[(int64_t)b * L + threadIdx.x] : 0.f;
-    const float dot = block_sum(a * d, red);
+    const float dot = block_reduce<false, 4>(a * d, red);
     if (threadIdx.x < L) { al[threadIdx.x] = a; ds[threadIdx.x] = a * (d - dot); }
   } else {                         // slots strided over the block, as in pool_out_kernel
     float ad = 0.f;
     for (int l = threadIdx.x; l < L; l += 256) ad += attn[(int64_t)b * L + l] * da[(int64_t)b * L + l];
-    const float dot = block_sum(ad, red);
+    const float dot = block_reduce<false, 4>(ad, red);
     for (int l = threadIdx.x; l < L; l += 256) {
       const float a = attn[(int64_t)b * L + l];
       al[l] = a;
@@ -609,25 +592,19 @@ __global__ __launch_bounds__(256) void rowdot_bwd_kernel(const T* __restrict__ x
 }
 }  // namespace
 
-#define ST(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" int goat_attn_pool_fwd(void* stream, int dtype, const void* x, const float* w, float* out, float* attn,
                                   float* ws, int B, int L, int H, const float* slot_mask) {
   if (!x || !w || !out || !attn || !ws) return GOAT_E_ARG;
   if (B <= 0 || L <= 0 || L > POOL_MAXL || H <= 0 || (H % 4)) return GOAT_E_SHAPE;
   const int rows = B * L;
   dim3 g1((rows + 3) / 4), g2(B, (H + 255) / 256);
-  if (dtype == GOAT_BF16) {
-    hipLaunchKernelGGL(pool_score_kernel<bf16_t>, g1, dim3(256), 0, ST(stream), (const bf16_t*)x, w, nullptr, nullptr, ws, rows, L, H, slot_mask);
-    hipLaunchKernelGGL(pool_out_kernel<bf16_t>, g2, dim3(256), 0, ST(stream), (const bf16_t*)x, ws, out, attn, L, H);
-  } else if (dtype == GOAT_F32) {
-    hipLaunchKernelGGL(pool_score_kernel<float>, g1, dim3(256), 0, ST(stream), (const float*)x, w, nullptr, nullptr, ws, rows, L, H, slot_mask);
-    hipLaunchKernelGGL(pool_out_kernel<float>, g2, dim3(256), 0, ST(stream), (const float*)x, ws, out, attn, L, H);
-  } else {
-    return GOAT_E_ARG;
-  }
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(pool_score_kernel<T>, g1, dim3(256), 0, ST(stream), (const T*)x, w, nullptr, nullptr, ws, rows, L, H, slot_mask);
+    hipLaunchKernelGGL(pool_out_kernel<T>, g2, dim3(256), 0, ST(stream), (const T*)x, ws, out, attn, L, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_attn_pool_bwd(void* stream, int dtype, const void* x, const float* w, const float* attn,
@@ -636,19 +613,14 @@ extern "C" int goat_attn_pool_bwd(void* stream, int dtype, const void* x, const 
   if (B <= 0 || L <= 0 || L > POOL_MAXL || H <= 0 || (H % 4)) return GOAT_E_SHAPE;
   const int rows = B * L;
   dim3 g1((rows + 3) / 4), g2(B, (H + 255) / 256);
-  if (dtype == GOAT_BF16) {
-    hipLaunchKernelGGL(pool_score_kernel<bf16_t>, g1, dim3(256), 0, ST(stream), (const bf16_t*)x, w, out, dout, ws, rows, L, H);
-    if (L <= 256) hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, false>), g2, dim3(256), 0, ST(stream), (const bf16_t*)x, w, attn, out, dout, ws, (bf16_t*)dx, dw, L, H);
-    else hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, true>), g2, dim3(256), 0, ST(stream), (const bf16_t*)x, w, attn, out, dout, ws, (bf16_t*)dx, dw, L, H);
-  } else if (dtype == GOAT_F32) {
-    hipLaunchKernelGGL(pool_score_kernel<float>, g1, dim3(256), 0, ST(stream), (const float*)x, w, out, dout, ws, rows, L, H);
-    if (L <= 256) hipLaunchKernelGGL((pool_bwd_kernel<float, false>), g2, dim3(256), 0, ST(stream), (const float*)x, w, attn, out, dout, ws, (float*)dx, dw, L, H);
-    else hipLaunchKernelGGL((pool_bwd_kernel<float, true>), g2, dim3(256), 0, ST(stream), (const float*)x, w, attn, out, dout, ws, (float*)dx, dw, L, H);
-  } else {
-    return GOAT_E_ARG;
-  }
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(pool_score_kernel<T>, g1, dim3(256), 0, ST(stream), (const T*)x, w, out, dout, ws, rows, L, H);
+    if (L <= 256) hipLaunchKernelGGL((pool_bwd_kernel<T, false>), g2, dim3(256), 0, ST(stream), (const T*)x, w, attn, out, dout, ws, (T*)dx, dw, L, H);
+    else hipLaunchKernelGGL((pool_bwd_kernel<T, true>), g2, dim3(256), 0, ST(stream), (const T*)x, w, attn, out, dout, ws, (T*)dx, dw, L, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_door_gate_fwd(void* stream, int dtype, const void* aug, const void* ori, const float* wa,
@@ -656,16 +628,13 @@ extern "C" int goat_door_gate_fwd(void* stream, int dtype, const void* aug, cons
   if (!aug || !ori || !wa || !wo || !ba || !bo || !out || !gate) return GOAT_E_ARG;
   if (rows <= 0 || H <= 0) return GOAT_E_SHAPE;
   const int blocks = (rows + 3) / 4;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(door_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST(stream), (const bf16_t*)aug, (const bf16_t*)ori,
-                       wa, wo, ba, bo, (bf16_t*)out, gate, rows, H);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(door_fwd_kernel<float>, dim3(blocks), dim3(256), 0, ST(stream), (const float*)aug, (const float*)ori,
-                       wa, wo, ba, bo, (float*)out, gate, rows, H);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(door_fwd_kernel<T>, dim3(blocks), dim3(256), 0, ST(stream), (const T*)aug, (const T*)ori, wa, wo, ba, bo,
+                       (T*)out, gate, rows, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_door_gate_bwd(void* stream, int dtype, const void* aug, const void* ori, const float* wa,
@@ -676,30 +645,25 @@ extern "C" int goat_door_gate_bwd(void* stream, int dtype, const void* aug, cons
   int blocks = (rows + 3) / 4;
   if (blocks > 256) blocks = 256;
   const size_t sm = (size_t)8 * H * sizeof(float);
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(door_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), sm, ST(stream), (const bf16_t*)aug, (const bf16_t*)ori,
-                       wa, wo, gate, (const bf16_t*)dout, (bf16_t*)daug, (bf16_t*)dori, dwa, dwo, dbias, dbias2, rows, H);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(door_bwd_kernel<float>, dim3(blocks), dim3(256), sm, ST(stream), (const float*)aug, (const float*)ori,
-                       wa, wo, gate, (const float*)dout, (float*)daug, (float*)dori, dwa, dwo, dbias, dbias2, rows, H);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(door_bwd_kernel<T>, dim3(blocks), dim3(256), sm, ST(stream), (const T*)aug, (const T*)ori, wa, wo, gate,
+                       (const T*)dout, (T*)daug, (T*)dori, dwa, dwo, dbias, dbias2, rows, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_dict_wsum_fwd(void* stream, int dtype_out, const float* z, const float* p, void* out, int B, int K,
                                   int H) {
   if (!z || !p || !out) return GOAT_E_ARG;
   if (B <= 0 || K <= 0 || H <= 0) return GOAT_E_SHAPE;
-  if (dtype_out == GOAT_BF16)
-    hipLaunchKernelGGL(dict_wsum_fwd_kernel<bf16_t>, dim3(B), dim3(256), 0, ST(stream), z, p, (bf16_t*)out, K, H);
-  else if (dtype_out == GOAT_F32)
-    hipLaunchKernelGGL(dict_wsum_fwd_kernel<float>, dim3(B), dim3(256), 0, ST(stream), z, p, (float*)out, K, H);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype_out, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(dict_wsum_fwd_kernel<T>, dim3(B), dim3(256), 0, ST(stream), z, p, (T*)out, K, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_dict_wsum_bwd(void* stream, int dtype_dout, const void* dout, const float* z, const float* p,
@@ -707,14 +671,12 @@ extern "C" int goat_dict_wsum_bwd(void* stream, int dtype_dout, const void* dout
   if (!dout || !z || !p) return GOAT_E_ARG;
   if (B <= 0 || K <= 0 || H <= 0) return GOAT_E_SHAPE;
   if (!dz && !dp) return 0;
-  if (dtype_dout == GOAT_BF16)
-    hipLaunchKernelGGL(dict_wsum_bwd_kernel<bf16_t>, dim3(B), dim3(256), 0, ST(stream), (const bf16_t*)dout, z, p, dz, dp, K, H);
-  else if (dtype_dout == GOAT_F32)
-    hipLaunchKernelGGL(dict_wsum_bwd_kernel<float>, dim3(B), dim3(256), 0, ST(stream), (const float*)dout, z, p, dz, dp, K, H);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype_dout, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(dict_wsum_bwd_kernel<T>, dim3(B), dim3(256), 0, ST(stream), (const T*)dout, z, p, dz, dp, K, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 // x_loc / txt_loc: [Bl, H]; x_all / txt_all: [Ba, H] (order gmap, vp, fused); gradients are ADDED to d* (pre-zeroed by the
@@ -742,7 +704,7 @@ extern "C" int goat_infonce_fwd(void* stream, const float* const* x_loc, const f
   if (int e = nce_fill(a, x_loc, x_all, txt_loc, txt_all, nullptr, nullptr, nullptr, nullptr, prob, Bl, Ba, H, target0, temperature)) return e;
   if ((size_t)Ba * 4 > 64 * 1024) return GOAT_E_SHAPE;
   a.loss = loss;
-  hipLaunchKernelGGL(infonce_fwd_kernel, dim3(Bl), dim3(256), (size_t)Ba * 4, reinterpret_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(infonce_fwd_kernel, dim3(Bl), dim3(256), (size_t)Ba * 4, ST(stream), a);
   GOAT_LAUNCH_CHECK();
   return 0;
 }
@@ -774,7 +736,7 @@ extern "C" int goat_infonce_bwd(void* stream, const float* const* x_loc, const f
   if (q.nroles == 0) return 0;
   q.row_groups = (Ba + 3) / 4;
   hipLaunchKernelGGL(infonce_bwd_kernel, dim3(q.nroles * q.row_groups, (H + 63) / 64), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), q);
+                     ST(stream), q);
   GOAT_LAUNCH_CHECK();
   return 0;
 }
@@ -783,14 +745,12 @@ extern "C" int goat_rowdot_fwd(void* stream, int dtype, const void* x, const flo
   if (!x || !w || !y) return GOAT_E_ARG;
   if (M <= 0 || H <= 0 || (H % 8)) return GOAT_E_SHAPE;
   const int blocks = (M + 3) / 4;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(rowdot_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST(stream), (const bf16_t*)x, w, b, (bf16_t*)y, M, H);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(rowdot_fwd_kernel<float>, dim3(blocks), dim3(256), 0, ST(stream), (const float*)x, w, b, (float*)y, M, H);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(rowdot_fwd_kernel<T>, dim3(blocks), dim3(256), 0, ST(stream), (const T*)x, w, b, (T*)y, M, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_rowdot_bwd(void* stream, int dtype, const void* x, const float* w, const void* dy, void* dx, float* dw, float* db, int M,
@@ -801,46 +761,38 @@ extern "C" int goat_rowdot_bwd(void* stream, int dtype, const void* x, const flo
   int blocks = (M + 3) / 4;
   if (blocks > 128) blocks = 128;          // (each block adds H + 1 partials atomically)
   const size_t sm = (size_t)4 * H * sizeof(float);
-  if (dtype == GOAT_BF16) {
-    if (H > 64 * 8 * 2) return GOAT_E_SHAPE;
-    hipLaunchKernelGGL((rowdot_bwd_kernel<bf16_t, 2>), dim3(blocks), dim3(256), sm, ST(stream), (const bf16_t*)x, w, (const bf16_t*)dy, (bf16_t*)dx,
-                       dw, db, M, H);
-  } else if (dtype == GOAT_F32) {
-    if (H > 64 * 4 * 4) return GOAT_E_SHAPE;
-    hipLaunchKernelGGL((rowdot_bwd_kernel<float, 4>), dim3(blocks), dim3(256), sm, ST(stream), (const float*)x, w, (const float*)dy, (float*)dx, dw,
-                       db, M, H);
-  } else {
-    return GOAT_E_ARG;
-  }
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    constexpr int MAXC = sizeof(T) == 2 ? 2 : 4;      // 16-byte chunks per lane: H <= 1024 either way
+    if (H > 64 * dt.EPC * MAXC) return GOAT_E_SHAPE;
+    hipLaunchKernelGGL((rowdot_bwd_kernel<T, MAXC>), dim3(blocks), dim3(256), sm, ST(stream), (const T*)x, w, (const T*)dy, (T*)dx, dw, db,
+                       M, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_cfp_mix_fwd(void* stream, int dtype_fwl, const float* go, const float* vo, const void* fwl, float* fo, float* fw, int B, int H) {
   if (!go || !vo || !fwl || !fo || !fw) return GOAT_E_ARG;
   if (B <= 0 || H <= 0) return GOAT_E_SHAPE;
-  if (dtype_fwl == GOAT_BF16)
-    hipLaunchKernelGGL(cfp_mix_fwd_kernel<bf16_t>, dim3(B), dim3(256), 0, ST(stream), go, vo, (const bf16_t*)fwl, fo, fw, H);
-  else if (dtype_fwl == GOAT_F32)
-    hipLaunchKernelGGL(cfp_mix_fwd_kernel<float>, dim3(B), dim3(256), 0, ST(stream), go, vo, (const float*)fwl, fo, fw, H);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype_fwl, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(cfp_mix_fwd_kernel<T>, dim3(B), dim3(256), 0, ST(stream), go, vo, (const T*)fwl, fo, fw, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_cfp_mix_bwd(void* stream, int dtype_fwl, const float* go, const float* vo, const float* fw, const float* dfo, float* dgo,
                                 float* dvo, void* dfwl, int B, int H, int accumulate) {
   if (!go || !vo || !fw || !dfo || !dgo || !dvo || !dfwl) return GOAT_E_ARG;
   if (B <= 0 || H <= 0) return GOAT_E_SHAPE;
-  if (dtype_fwl == GOAT_BF16)
-    hipLaunchKernelGGL(cfp_mix_bwd_kernel<bf16_t>, dim3(B), dim3(256), 0, ST(stream), go, vo, fw, dfo, dgo, dvo, (bf16_t*)dfwl, H, accumulate);
-  else if (dtype_fwl == GOAT_F32)
-    hipLaunchKernelGGL(cfp_mix_bwd_kernel<float>, dim3(B), dim3(256), 0, ST(stream), go, vo, fw, dfo, dgo, dvo, (float*)dfwl, H, accumulate);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype_fwl, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(cfp_mix_bwd_kernel<T>, dim3(B), dim3(256), 0, ST(stream), go, vo, fw, dfo, dgo, dvo, (T*)dfwl, H, accumulate);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 static int sap_check(const SapArgs& a, int dtype) {
@@ -861,10 +813,11 @@ extern "C" int goat_sap_fuse_fwd(void* stream, int dtype, const void* gs, const 
   if (int e = sap_check(a, dtype)) return e;
   if (loss && !lse) return GOAT_E_ARG;
   const size_t smem = (size_t)(2 * G + 2 * W) * 4;
-  if (dtype == GOAT_BF16) hipLaunchKernelGGL(sap_fwd_kernel<bf16_t>, dim3(B), dim3(64), smem, reinterpret_cast<hipStream_t>(stream), a);
-  else hipLaunchKernelGGL(sap_fwd_kernel<float>, dim3(B), dim3(64), smem, reinterpret_cast<hipStream_t>(stream), a);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    hipLaunchKernelGGL(sap_fwd_kernel<GOAT_DT_TYPE(dt)>, dim3(B), dim3(64), smem, ST(stream), a);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_sap_fuse_bwd(void* stream, int dtype, const void* gs, const void* ls, const void* fwl, int fw_sigmoid,
@@ -881,8 +834,9 @@ extern "C" int goat_sap_fuse_bwd(void* stream, int dtype, const void* gs, const 
   if (int e = sap_check(a, dtype)) return e;
   if (!dgs || !dls || (dloss && !lse) || (fwl && !dfwl)) return GOAT_E_ARG;
   const size_t smem = (size_t)G * 4;
-  if (dtype == GOAT_BF16) hipLaunchKernelGGL(sap_bwd_kernel<bf16_t>, dim3(B), dim3(64), smem, reinterpret_cast<hipStream_t>(stream), a);
-  else hipLaunchKernelGGL(sap_bwd_kernel<float>, dim3(B), dim3(64), smem, reinterpret_cast<hipStream_t>(stream), a);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    hipLaunchKernelGGL(sap_bwd_kernel<GOAT_DT_TYPE(dt)>, dim3(B), dim3(64), smem, ST(stream), a);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }

@@ -19,10 +19,12 @@ typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4;
 
 template <typename T> struct DT;
 template <> struct DT<float> {
+  typedef float type;
   static constexpr int id = GOAT_F32;
   static constexpr int EPC = 4;  // elements per 16-byte chunk
 };
 template <> struct DT<bf16_t> {
+  typedef bf16_t type;
   static constexpr int id = GOAT_BF16;
   static constexpr int EPC = 8;
 };
@@ -198,6 +200,20 @@ __device__ __forceinline__ float half_max(float v) {
   for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// block-wide max / sum over the NWAVES waves of a block through `buf` (one float per wave); every thread gets the result.  The
+// per-wave partials are combined in ascending wave order: a sum is bitwise reproducible.
+template <bool MAX, int NWAVES>
+__device__ __forceinline__ float block_reduce(float v, float* buf) {
+  v = MAX ? wave_max(v) : wave_sum(v);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();                      // (buf may still be read from the previous reduction)
+  if (lane == 0) buf[wave] = v;
+  __syncthreads();
+  float r = buf[0];
+#pragma unroll
+  for (int w = 1; w < NWAVES; ++w) r = MAX ? fmaxf(r, buf[w]) : r + buf[w];
+  return r;
+}
 
 // ---- MFMA 32x32 tile step on a pair of 16-byte operand chunks --------------------------------------
 // Lane l holds, for A: row (l&31) of the 32-row tile, the 16-byte k-chunk number (l>>5) of a 32-byte
@@ -281,3 +297,17 @@ __device__ __forceinline__ float dgelu_fast(float x) {
   return dgelu_f(x);
 #endif
 }
+
+// ---- host side of the extern "C" launchers ---------------------------------------------------------
+inline hipStream_t ST(void* stream) { return reinterpret_cast<hipStream_t>(stream); }
+
+// Calls f(DT<bf16_t>{}) or f(DT<float>{}) for the dtype code of the C ABI and returns what it returns; any other code is
+// GOAT_E_ARG.  Launchers call it AFTER their pointer and shape checks (a null pointer wins over a bad dtype) and write the launch
+// once, with `typename decltype(dt)::type` as the element type; limits that depend on the dtype stay inside f.
+template <typename F>
+int dtype_dispatch(int dtype, F&& f) {
+  if (dtype == GOAT_BF16) return f(DT<bf16_t>{});
+  if (dtype == GOAT_F32) return f(DT<float>{});
+  return GOAT_E_ARG;
+}
+#define GOAT_DT_TYPE(dt_) typename decltype(dt_)::type

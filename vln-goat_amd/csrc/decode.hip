@@ -37,19 +37,6 @@ struct DecodeArgs {
   const uint64_t* rng_dev;
 };
 
-// block-wide max / sum over DEC_THREADS threads through `buf` (one float per wave); every thread gets the result
-template <bool MAX>
-__device__ __forceinline__ float block_reduce(float v, float* buf, int tid) {
-  v = MAX ? wave_max(v) : wave_sum(v);
-  __syncthreads();                      // (buf may still be read from the previous reduction)
-  if ((tid & 63) == 0) buf[tid >> 6] = v;
-  __syncthreads();
-  float r = buf[0];
-#pragma unroll
-  for (int w = 1; w < DEC_THREADS / 64; ++w) r = MAX ? fmaxf(r, buf[w]) : r + buf[w];
-  return r;
-}
-
 template <typename T>
 __global__ __launch_bounds__(DEC_THREADS) void attn_decode_kernel(DecodeArgs a) {
   constexpr int NE = DT<T>::EPC;              // elements per 16-byte chunk
@@ -100,7 +87,7 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_kernel(DecodeArgs a) 
     s[i] = v;
     m = fmaxf(m, v);
   }
-  m = block_reduce<true>(m, wbuf, tid);
+  m = block_reduce<true, DEC_THREADS / 64>(m, wbuf);
   const float msafe = (m == -INFINITY) ? 0.f : m;       // every visible key at -inf: exp(-inf - 0) = 0, never inf - inf
   float l = 0.f;
 #pragma unroll
@@ -108,7 +95,7 @@ __global__ __launch_bounds__(DEC_THREADS) void attn_decode_kernel(DecodeArgs a) 
     s[i] = (tid + i * DEC_THREADS <= t) ? __expf(s[i] - msafe) : 0.f;
     l += s[i];
   }
-  l = block_reduce<false>(l, wbuf, tid);
+  l = block_reduce<false, DEC_THREADS / 64>(l, wbuf);
   const float inv = l > 0.f ? 1.f / l : 0.f;
 
   const bool drop = a.p > 0.f;
@@ -237,13 +224,11 @@ extern "C" int goat_attn_decode_fwd(void* stream, int dtype, const void* Q, cons
   a.Q = Q; a.KVnew = KVnew; a.cache = cache; a.O = O;
   a.c_rs = c_rs; a.c_bs = c_bs; a.kmask = kmask; a.pos = pos_dev;
   a.B = B; a.nh = nh; a.Lmax = Lmax; a.scale = scale; a.p = p; a.seed = seed; a.offset = offset; a.rng_dev = rng_dev;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(attn_decode_kernel<bf16_t>, dim3(B * nh), dim3(DEC_THREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL(attn_decode_kernel<float>, dim3(B * nh), dim3(DEC_THREADS), 0, st, a);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    hipLaunchKernelGGL(attn_decode_kernel<GOAT_DT_TYPE(dt)>, dim3(B * nh), dim3(DEC_THREADS), 0, ST(stream), a);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_decode_select(void* stream, const float* logits, int64_t ld, int B, int V, int Lmax, int unk, int eos, int pad,
@@ -255,7 +240,7 @@ extern "C" int goat_decode_select(void* stream, const float* logits, int64_t ld,
   a.logits = logits; a.ld = ld; a.B = B; a.V = V; a.Lmax = Lmax; a.unk = unk; a.eos = eos; a.pad = pad; a.sampling = sampling;
   a.seed = seed; a.offset = offset; a.rng_dev = rng_dev; a.pos = pos_dev;
   a.words = words; a.kmask = kmask; a.ended = ended; a.end_step = end_step; a.n_live = n_live;
-  hipLaunchKernelGGL(decode_select_kernel, dim3(1), dim3(64 * SEL_WAVES), 0, reinterpret_cast<hipStream_t>(stream), a);
+  hipLaunchKernelGGL(decode_select_kernel, dim3(1), dim3(64 * SEL_WAVES), 0, ST(stream), a);
   GOAT_LAUNCH_CHECK();
   return 0;
 }

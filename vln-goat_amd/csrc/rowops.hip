@@ -616,7 +616,9 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, in
 //   fwd: lse[m] = logsumexp(logits[m,:N]) ; loss[m] = lse - logits[m, target]       (F.cross_entropy, reduction none;
 //        P/model/pretrain_goat.py:213-215 on the 576 x 50265 MLM scores)
 //   bwd: dlogits[m,n] = (exp(l - lse) - [n == target]) * dloss[m] for n < N, 0 for the padding columns n in [N, ld_out)
-__device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
+// (not common.hpp's block_reduce: this one takes the wave count from the block it runs in, and folding it into the shared template
+// reorders ce_fwd_kernel's instructions; the kernel is kept as it was)
+__device__ __forceinline__ float block_reduce_dyn(float v, float* red, bool is_max) {
   v = is_max ? wave_max(v) : wave_sum(v);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   __syncthreads();
@@ -640,14 +642,14 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
     mx = fmaxf(fmaxf(mx, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
   }
   for (int c = n4 * 4 + threadIdx.x; c < N; c += 256) mx = fmaxf(mx, row[c]);
-  mx = block_reduce(mx, red, true);
+  mx = block_reduce_dyn(mx, red, true);
   float sum = 0.f;
   for (int c = threadIdx.x; c < n4; c += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(row + c * 4);
     sum += __expf(v[0] - mx) + __expf(v[1] - mx) + __expf(v[2] - mx) + __expf(v[3] - mx);
   }
   for (int c = n4 * 4 + threadIdx.x; c < N; c += 256) sum += __expf(row[c] - mx);
-  sum = block_reduce(sum, red, false);
+  sum = block_reduce_dyn(sum, red, false);
   if (threadIdx.x == 0) {
     const float l = mx + __logf(sum);
     lse[m] = l;
@@ -1251,8 +1253,6 @@ int ln_maxc(int H) {  // smallest instantiated chunk count covering H
 
 }  // namespace
 
-#define ST(s) reinterpret_cast<hipStream_t>(s)
-
 extern "C" int goat_version(void) { return 103; }
 
 extern "C" int goat_ln_fwd_do(void* stream, int dtype, const void* x, const void* residual, const float* gamma,
@@ -1263,23 +1263,15 @@ extern "C" int goat_ln_fwd_do(void* stream, int dtype, const void* x, const void
   if (M <= 0 || !(p_out >= 0.f && p_out < 1.f)) return GOAT_E_SHAPE;
   if ((residual || p > 0.f) && !z_out) return GOAT_E_ARG;
   dim3 grid((M + 3) / 4);
-  if (dtype == GOAT_BF16) {
-    if (int e = ln_check<bf16_t>(H)) return e;
-    GOAT_LN_DISPATCH(bf16_t, H, hipLaunchKernelGGL((ln_fwd_kernel<bf16_t, MC>), grid, dim3(256), 0, ST(stream),
-                                                    (const bf16_t*)x, (const bf16_t*)residual, gamma, beta, eps, p, seed,
-                                                    offset, rng_dev, (bf16_t*)y, (bf16_t*)z_out, mean, rstd, M, H, p_out, offset_out,
-                                                    (const bf16_t*)post_add));
-  } else if (dtype == GOAT_F32) {
-    if (int e = ln_check<float>(H)) return e;
-    GOAT_LN_DISPATCH(float, H, hipLaunchKernelGGL((ln_fwd_kernel<float, MC>), grid, dim3(256), 0, ST(stream),
-                                                   (const float*)x, (const float*)residual, gamma, beta, eps, p, seed,
-                                                   offset, rng_dev, (float*)y, (float*)z_out, mean, rstd, M, H, p_out, offset_out,
-                                                   (const float*)post_add));
-  } else {
-    return GOAT_E_ARG;
-  }
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    if (int e = ln_check<T>(H)) return e;
+    GOAT_LN_DISPATCH(T, H, hipLaunchKernelGGL((ln_fwd_kernel<T, MC>), grid, dim3(256), 0, ST(stream), (const T*)x, (const T*)residual, gamma,
+                                              beta, eps, p, seed, offset, rng_dev, (T*)y, (T*)z_out, mean, rstd, M, H, p_out, offset_out,
+                                              (const T*)post_add));
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_ln_fwd(void* stream, int dtype, const void* x, const void* residual, const float* gamma,
@@ -1331,7 +1323,7 @@ extern "C" int goat_ln_reduce_batched(void* stream, const goat_ln_partial* entri
       if (!e.ws || !e.dgamma || !e.dbeta || e.nparts <= 0) return GOAT_E_ARG;
       a.e[k].ws = e.ws; a.e[k].dgamma = e.dgamma; a.e[k].dbeta = e.dbeta; a.e[k].nparts = e.nparts; a.e[k].pad = 0;
     }
-    hipLaunchKernelGGL(ln_reduce_batched_kernel, dim3((2 * H + 15) / 16, a.n), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(ln_reduce_batched_kernel, dim3((2 * H + 15) / 16, a.n), dim3(256), 0, ST(stream), a);
     GOAT_LAUNCH_CHECK();
   }
   return 0;
@@ -1445,16 +1437,13 @@ extern "C" int goat_dropout_add_fwd(void* stream, int dtype, const void* x, cons
   int64_t blocks = (n / 8 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL((dropout_kernel<bf16_t, false>), dim3((int)blocks), dim3(256), 0, ST(stream), (const bf16_t*)x,
-                       (const bf16_t*)residual, (bf16_t*)y, n, p, seed, offset, rng_dev);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL((dropout_kernel<float, false>), dim3((int)blocks), dim3(256), 0, ST(stream), (const float*)x,
-                       (const float*)residual, (float*)y, n, p, seed, offset, rng_dev);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL((dropout_kernel<T, false>), dim3((int)blocks), dim3(256), 0, ST(stream), (const T*)x, (const T*)residual, (T*)y, n, p,
+                       seed, offset, rng_dev);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_dropout_bwd(void* stream, int dtype, const void* dy, void* dx, int64_t n, float p, uint64_t seed,
@@ -1464,16 +1453,13 @@ extern "C" int goat_dropout_bwd(void* stream, int dtype, const void* dy, void* d
   int64_t blocks = (n / 8 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL((dropout_kernel<bf16_t, true>), dim3((int)blocks), dim3(256), 0, ST(stream), (const bf16_t*)dy,
-                       (const bf16_t*)nullptr, (bf16_t*)dx, n, p, seed, offset, rng_dev);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL((dropout_kernel<float, true>), dim3((int)blocks), dim3(256), 0, ST(stream), (const float*)dy,
-                       (const float*)nullptr, (float*)dx, n, p, seed, offset, rng_dev);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL((dropout_kernel<T, true>), dim3((int)blocks), dim3(256), 0, ST(stream), (const T*)dy, (const T*)nullptr, (T*)dx, n, p,
+                       seed, offset, rng_dev);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_act_bwd(void* stream, int dtype, const void* dy, const void* u, void* dx, int64_t n, int act,
@@ -1484,16 +1470,13 @@ extern "C" int goat_act_bwd(void* stream, int dtype, const void* dy, const void*
   int64_t blocks = (n / 8 + 255) / 256;
   if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3((int)blocks), dim3(256), 0, ST(stream), (const bf16_t*)dy,
-                       (const bf16_t*)u, (bf16_t*)dx, n, act, p, seed, offset, rng_dev);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(act_bwd_kernel<float>, dim3((int)blocks), dim3(256), 0, ST(stream), (const float*)dy,
-                       (const float*)u, (float*)dx, n, act, p, seed, offset, rng_dev);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(act_bwd_kernel<T>, dim3((int)blocks), dim3(256), 0, ST(stream), (const T*)dy, (const T*)u, (T*)dx, n, act, p, seed,
+                       offset, rng_dev);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_colsum(void* stream, int dtype, const void* x, int64_t ld, int R, int C, float* colsum) {
@@ -1505,16 +1488,12 @@ extern "C" int goat_colsum(void* stream, int dtype, const void* x, int64_t ld, i
   if (rb < 1) rb = 1;
   const int rows_per_block = (R + rb - 1) / rb;
   dim3 grid(cb, (R + rows_per_block - 1) / rows_per_block);
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, ST(stream), (const bf16_t*)x, ld, R, C, colsum,
-                       rows_per_block);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, ST(stream), (const float*)x, ld, R, C, colsum,
-                       rows_per_block);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, ST(stream), (const T*)x, ld, R, C, colsum, rows_per_block);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_ce_fwd(void* stream, const float* logits, int64_t ld, int M, int N, const int64_t* targets,
@@ -1530,16 +1509,12 @@ extern "C" int goat_ce_bwd(void* stream, int dtype_out, const float* logits, int
                            const int64_t* targets, const float* lse, const float* dloss, void* dlogits, int64_t ld_out) {
   if (!logits || !targets || !lse || !dloss || !dlogits) return GOAT_E_ARG;
   if (M <= 0 || N <= 0 || ld < N || ld_out < N) return GOAT_E_SHAPE;
-  if (dtype_out == GOAT_BF16)
-    hipLaunchKernelGGL(ce_bwd_kernel<bf16_t>, dim3(M), dim3(256), 0, ST(stream), logits, ld, N, targets, lse, dloss,
-                       (bf16_t*)dlogits, ld_out);
-  else if (dtype_out == GOAT_F32)
-    hipLaunchKernelGGL(ce_bwd_kernel<float>, dim3(M), dim3(256), 0, ST(stream), logits, ld, N, targets, lse, dloss,
-                       (float*)dlogits, ld_out);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype_out, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(ce_bwd_kernel<T>, dim3(M), dim3(256), 0, ST(stream), logits, ld, N, targets, lse, dloss, (T*)dlogits, ld_out);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_transpose(void* stream, int dtype, const void* in, int64_t ld_in, void* out, int64_t ld_out, int R,
@@ -1550,16 +1525,12 @@ extern "C" int goat_transpose(void* stream, int dtype, const void* in, int64_t l
   int RT = 1;
   while (RT < 16 && (int64_t)((rtiles + 2 * RT - 1) / (2 * RT)) * ctiles >= 1024) RT *= 2;
   dim3 grid((rtiles + RT - 1) / RT, ctiles);
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(transpose_kernel<bf16_t>, grid, dim3(256), 0, ST(stream), (const bf16_t*)in, ld_in, (bf16_t*)out,
-                       ld_out, R, C, colsum, RT);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(transpose_kernel<float>, grid, dim3(256), 0, ST(stream), (const float*)in, ld_in, (float*)out,
-                       ld_out, R, C, colsum, RT);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(transpose_kernel<T>, grid, dim3(256), 0, ST(stream), (const T*)in, ld_in, (T*)out, ld_out, R, C, colsum, RT);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_wgrad_smallk(void* stream, int dtype, const void* dy, int64_t ld_dy, const void* x, int64_t ld_x, int rows,
@@ -1601,25 +1572,16 @@ extern "C" int goat_pano_fusion_fwd(void* stream, int dtype, const void* x, cons
 #ifdef GOAT_PANO_GENERIC
   sm = 1 << 30;
 #endif
-  if (dtype == GOAT_BF16) {
-    if (H % 8 == 0 && H <= 64 * 8 * 2 && sm <= 64 * 1024)
-      hipLaunchKernelGGL((pano_fusion_fwd_kernel<bf16_t, 2>), dim3(N), dim3(64 * PF_NW), sm, ST(stream), (const bf16_t*)x, a, a0,
-                         (bf16_t*)fused, wsave, V, H);
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    constexpr int MC = sizeof(T) == 2 ? 2 : 3;      // 16-byte chunks per lane of the register kernel: H <= 1024 bf16, 768 f32
+    if (H % dt.EPC == 0 && H <= 64 * dt.EPC * MC && sm <= 64 * 1024)
+      hipLaunchKernelGGL((pano_fusion_fwd_kernel<T, MC>), dim3(N), dim3(64 * PF_NW), sm, ST(stream), (const T*)x, a, a0, (T*)fused, wsave, V, H);
     else
-      hipLaunchKernelGGL(pano_fusion_fwd_generic<bf16_t>, dim3(N), dim3(256), 0, ST(stream), (const bf16_t*)x, a, a0,
-                         (bf16_t*)fused, wsave, V, H);
-  } else if (dtype == GOAT_F32) {
-    if (H % 4 == 0 && H <= 64 * 4 * 3 && sm <= 64 * 1024)
-      hipLaunchKernelGGL((pano_fusion_fwd_kernel<float, 3>), dim3(N), dim3(64 * PF_NW), sm, ST(stream), (const float*)x, a, a0,
-                         (float*)fused, wsave, V, H);
-    else
-      hipLaunchKernelGGL(pano_fusion_fwd_generic<float>, dim3(N), dim3(256), 0, ST(stream), (const float*)x, a, a0,
-                         (float*)fused, wsave, V, H);
-  } else {
-    return GOAT_E_ARG;
-  }
-  GOAT_LAUNCH_CHECK();
-  return 0;
+      hipLaunchKernelGGL(pano_fusion_fwd_generic<T>, dim3(N), dim3(256), 0, ST(stream), (const T*)x, a, a0, (T*)fused, wsave, V, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_pano_fusion_bwd(void* stream, int dtype, const void* x, const float* a, const float* a0,
@@ -1631,25 +1593,18 @@ extern "C" int goat_pano_fusion_bwd(void* stream, int dtype, const void* x, cons
 #ifdef GOAT_PANO_GENERIC
   sm = 1 << 30;
 #endif
-  if (dtype == GOAT_BF16) {
-    if (H % 8 == 0 && H <= 64 * 8 * 2 && sm <= 64 * 1024)
-      hipLaunchKernelGGL((pano_fusion_bwd_kernel<bf16_t, 2>), dim3(N), dim3(64 * PF_NW), sm, ST(stream), (const bf16_t*)x, a, a0,
-                         wsave, (const bf16_t*)dfused, (bf16_t*)dx, da, da0, V, H);
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    constexpr int MC = sizeof(T) == 2 ? 2 : 3;
+    if (H % dt.EPC == 0 && H <= 64 * dt.EPC * MC && sm <= 64 * 1024)
+      hipLaunchKernelGGL((pano_fusion_bwd_kernel<T, MC>), dim3(N), dim3(64 * PF_NW), sm, ST(stream), (const T*)x, a, a0, wsave, (const T*)dfused,
+                         (T*)dx, da, da0, V, H);
     else
-      hipLaunchKernelGGL(pano_fusion_bwd_generic<bf16_t>, dim3(N), dim3(256), 0, ST(stream), (const bf16_t*)x, a, a0,
-                         wsave, (const bf16_t*)dfused, (bf16_t*)dx, da, da0, V, H);
-  } else if (dtype == GOAT_F32) {
-    if (H % 4 == 0 && H <= 64 * 4 * 3 && sm <= 64 * 1024)
-      hipLaunchKernelGGL((pano_fusion_bwd_kernel<float, 3>), dim3(N), dim3(64 * PF_NW), sm, ST(stream), (const float*)x, a, a0, wsave,
-                         (const float*)dfused, (float*)dx, da, da0, V, H);
-    else
-      hipLaunchKernelGGL(pano_fusion_bwd_generic<float>, dim3(N), dim3(256), 0, ST(stream), (const float*)x, a, a0, wsave,
-                         (const float*)dfused, (float*)dx, da, da0, V, H);
-  } else {
-    return GOAT_E_ARG;
-  }
-  GOAT_LAUNCH_CHECK();
-  return 0;
+      hipLaunchKernelGGL(pano_fusion_bwd_generic<T>, dim3(N), dim3(256), 0, ST(stream), (const T*)x, a, a0, wsave, (const T*)dfused, (T*)dx, da,
+                         da0, V, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_gather_segmean_fwd(void* stream, int dtype, const void* src, int64_t src_rows, const int32_t* idx,
@@ -1661,16 +1616,12 @@ extern "C" int goat_gather_segmean_fwd(void* stream, int dtype, const void* src,
   int64_t total = (int64_t)n_out * (H / epc);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(gather_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST(stream), (const bf16_t*)src, idx, start,
-                       scale, tok_w, (bf16_t*)out, n_out, H);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(gather_fwd_kernel<float>, dim3(blocks), dim3(256), 0, ST(stream), (const float*)src, idx, start,
-                       scale, tok_w, (float*)out, n_out, H);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(gather_fwd_kernel<T>, dim3(blocks), dim3(256), 0, ST(stream), (const T*)src, idx, start, scale, tok_w, (T*)out, n_out, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_gather_segmean_bwd(void* stream, int dtype, const void* dout, const int32_t* idx,
@@ -1682,16 +1633,12 @@ extern "C" int goat_gather_segmean_bwd(void* stream, int dtype, const void* dout
   int64_t total = (int64_t)n_out * (H / epc);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(gather_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST(stream), (const bf16_t*)dout, idx, start,
-                       scale, dsrc32, n_out, H);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(gather_bwd_kernel<float>, dim3(blocks), dim3(256), 0, ST(stream), (const float*)dout, idx, start,
-                       scale, dsrc32, n_out, H);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(gather_bwd_kernel<T>, dim3(blocks), dim3(256), 0, ST(stream), (const T*)dout, idx, start, scale, dsrc32, n_out, H);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_embed_fwd(void* stream, int dtype, const float* word, const int64_t* ids, const float* type_tab,
@@ -1704,16 +1651,13 @@ extern "C" int goat_embed_fwd(void* stream, int dtype, const float* word, const 
   int64_t total = (int64_t)rows * (H / epc);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(embed_fwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST(stream), word, ids, type_tab, type_ids,
-                       pos_tab, L, (bf16_t*)out, rows, H, vocab, err_flag);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(embed_fwd_kernel<float>, dim3(blocks), dim3(256), 0, ST(stream), word, ids, type_tab, type_ids,
-                       pos_tab, L, (float*)out, rows, H, vocab, err_flag);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(embed_fwd_kernel<T>, dim3(blocks), dim3(256), 0, ST(stream), word, ids, type_tab, type_ids, pos_tab, L, (T*)out, rows, H,
+                       vocab, err_flag);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_embed_bwd(void* stream, int dtype, const void* dout, const int64_t* ids, const int64_t* type_ids,
@@ -1727,29 +1671,22 @@ extern "C" int goat_embed_bwd(void* stream, int dtype, const void* dout, const i
   if (!es_off && dword && !dtype_tab && !dpos && vocab <= ES_MAXV && rows >= 512) {      // single small table: LDS accumulation per block
     dim3 grid((H + 63) / 64, (rows + ES_ROWS - 1) / ES_ROWS);
     const size_t sm = (size_t)4 * vocab * 64 * sizeof(float);
-    if (dtype == GOAT_BF16)
-      hipLaunchKernelGGL(embed_bwd_small_kernel<bf16_t>, grid, dim3(256), sm, ST(stream), (const bf16_t*)dout, ids, dword, rows, H, vocab,
-                         word_pad);
-    else if (dtype == GOAT_F32)
-      hipLaunchKernelGGL(embed_bwd_small_kernel<float>, grid, dim3(256), sm, ST(stream), (const float*)dout, ids, dword, rows, H, vocab,
-                         word_pad);
-    else
-      return GOAT_E_ARG;
-    GOAT_LAUNCH_CHECK();
-    return 0;
+    return dtype_dispatch(dtype, [&](auto dt) -> int {
+      typedef GOAT_DT_TYPE(dt) T;
+      hipLaunchKernelGGL(embed_bwd_small_kernel<T>, grid, dim3(256), sm, ST(stream), (const T*)dout, ids, dword, rows, H, vocab, word_pad);
+      GOAT_LAUNCH_CHECK();
+      return 0;
+    });
   }
   int blocks = (rows + 3) / 4;
   if (blocks > 8192) blocks = 8192;
-  if (dtype == GOAT_BF16)
-    hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, dim3(blocks), dim3(256), 0, ST(stream), (const bf16_t*)dout, ids, type_ids,
-                       L, dword, dtype_tab, dpos, rows, H, vocab, word_pad, pos_pad);
-  else if (dtype == GOAT_F32)
-    hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3(blocks), dim3(256), 0, ST(stream), (const float*)dout, ids, type_ids,
-                       L, dword, dtype_tab, dpos, rows, H, vocab, word_pad, pos_pad);
-  else
-    return GOAT_E_ARG;
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return dtype_dispatch(dtype, [&](auto dt) -> int {
+    typedef GOAT_DT_TYPE(dt) T;
+    hipLaunchKernelGGL(embed_bwd_kernel<T>, dim3(blocks), dim3(256), 0, ST(stream), (const T*)dout, ids, type_ids, L, dword, dtype_tab, dpos,
+                       rows, H, vocab, word_pad, pos_pad);
+    GOAT_LAUNCH_CHECK();
+    return 0;
+  });
 }
 
 extern "C" int goat_probe_tr16(void* stream, uint16_t* out) {
