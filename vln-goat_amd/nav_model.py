@@ -11,248 +11,14 @@ import collections
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 from torch import nn
 
-from . import graphmap, hipops
-from .layers import (BertAttention, BertLayerNorm, BertPooler, BertPredictionHeadTransform, ClsPrediction,
-                     CrossmodalEncoder, Linear, RobertaAttention, RobertaEmbeddings, RobertaLayer, _p, compute_dtype, project_kv_bank,
-                     create_transformer_encoder, gen_seq_masks, neg_mask)
+from . import hipops
+from .encoders import (CausalImageEmbeddings, GlobalMapEncoder, LanguageEncoder, LanguageEncoderDo, LocalVPEncoder, _door,  # noqa: F401
+                       trajectory_indices)
+from .layers import (BertAttention, BertLayerNorm, BertPooler, BertPredictionHeadTransform, ClsPrediction, Linear, RobertaEmbeddings,
+                     _p, compute_dtype, neg_mask, project_kv_bank)
 from .pretrain_model import GoatPreTrainedModel, attn_pool
-
-
-def _door(aug_lin, ori_lin, aug, ori):
-    """door gate: w = sigmoid(Linear_a(aug) + Linear_o(ori)); out = w*aug + (1-w)*ori
-    (M/models/vilmodel_GOAT.py:147-153, 548-552)."""
-    return hipops.door_gate(aug_lin, ori_lin, aug, ori)
-
-
-class LanguageEncoder(nn.Module):
-    def __init__(self, config):
-        super().__init__()
-        self.num_l_layers = config.num_l_layers
-        self.update_lang_bert = config.update_lang_bert
-        self.layer = nn.ModuleList([RobertaLayer(config) for _ in range(self.num_l_layers)])
-        if not self.update_lang_bert:
-            for _, p in self.layer.named_parameters():
-                p.requires_grad = False
-
-    def forward(self, txt_embeds, txt_masks, *unused):
-        km = neg_mask(txt_masks)
-        for i, layer in enumerate(self.layer):       # between layers the state travels as a layers._pair (fork=True)
-            txt_embeds = layer(txt_embeds, km, fork=i + 1 < len(self.layer))
-        return txt_embeds if self.update_lang_bert else txt_embeds.detach()
-
-
-class LanguageEncoderDo(nn.Module):
-    """M/models/vilmodel_GOAT.py:55-162 (BACL-txt type_1 / type_2, FACL-txt, door / add / concat)."""
-
-    def __init__(self, config):
-        super().__init__()
-        self.config = config
-        self.num_l_layers = config.num_l_layers
-        self.update_lang_bert = config.update_lang_bert
-        self.layer = nn.ModuleList([RobertaLayer(config) for _ in range(self.num_l_layers)])
-        if not self.update_lang_bert:
-            for _, p in self.layer.named_parameters():
-                p.requires_grad = False
-        H = config.hidden_size
-        if config.do_back_txt or config.do_front_txt:
-            self.z_txt_linear = Linear(H, H)
-            self.z_direct_linear = Linear(H, H)
-            self.z_landm_linear = Linear(H, H)
-            self.z_concat_layernorm = BertLayerNorm(H, eps=config.layer_norm_eps)
-            self.z_direct_ln = BertLayerNorm(H, eps=config.layer_norm_eps)
-            self.z_landm_ln = BertLayerNorm(H, eps=config.layer_norm_eps)
-            if config.do_back_txt_type == 'type_2':
-                self.z_direc_cross_attn = RobertaAttention(config)
-                self.z_landm_cross_attn = RobertaAttention(config)
-                self.instr_aug_linear = Linear(H, 1)
-                self.instr_ori_linear = Linear(H, 1)
-                self.instr_sigmoid = nn.Sigmoid()
-                self.concat_linear = Linear(H * 3, H)
-        if config.do_front_txt:
-            self.z_front_cross_attn = RobertaAttention(config)
-            self.z_front_linear = Linear(H, H)
-            self.z_front_ln = BertLayerNorm(H, eps=config.layer_norm_eps)
-        self.dropout = nn.Dropout(config.hidden_dropout_prob)
-
-    def forward(self, txt_embeds, txt_masks, z_direc=None, z_direc_pzs=None, z_landm=None, z_landm_pzs=None, front_txt=None):
-        cfg = self.config
-        km = neg_mask(txt_masks)
-        for i, layer in enumerate(self.layer):       # between layers the state travels as a layers._pair (fork=True)
-            txt_embeds = layer(txt_embeds, km, fork=i + 1 < len(self.layer))
-        if not self.update_lang_bert:
-            txt_embeds = txt_embeds.detach()
-        if not (cfg.do_back_txt or cfg.do_front_txt):
-            return txt_embeds
-        dt = txt_embeds.dtype
-        z_front = None
-        if cfg.do_back_txt_type == 'type_1':
-            if cfg.do_back_txt:
-                sd = hipops.dict_weighted_sum(z_direc, z_direc_pzs, dt)
-                sl = hipops.dict_weighted_sum(z_landm, z_landm_pzs, dt)
-                txt_embeds = self.z_txt_linear(txt_embeds) + self.z_direct_linear(sd) + self.z_landm_linear(sl)
-            if cfg.do_front_txt and front_txt is not None:
-                zf = self.z_front_cross_attn(txt_embeds, None, front_txt.to(dt), None)
-                txt_embeds = txt_embeds + self.z_front_ln(self.z_front_linear(zf))
-            return self.z_concat_layernorm(txt_embeds)
-        # type_2: cross-attention of the text over each confounder dictionary (no key mask)
-        zd = zl = None
-        if cfg.do_back_txt:
-            zd = self.z_direct_ln(self.z_direct_linear(self.z_direc_cross_attn(txt_embeds, None, z_direc.to(dt), None)))
-            if z_landm is not None:
-                zl = self.z_landm_ln(self.z_landm_linear(self.z_landm_cross_attn(txt_embeds, None, z_landm.to(dt), None)))
-        if cfg.do_front_txt and front_txt is not None:
-            z_front = self.z_front_ln(self.z_front_linear(self.z_front_cross_attn(txt_embeds, None, front_txt.to(dt), None)))
-        if cfg.do_add_method == 'door':
-            aug = None
-            if cfg.do_back_txt:
-                aug = zd
-                if zl is not None:
-                    aug = aug + zl
-                if front_txt is not None:
-                    aug = aug + z_front
-            elif cfg.do_front_txt and front_txt is not None:
-                aug = z_front
-            txt_embeds = _door(self.instr_aug_linear, self.instr_ori_linear, aug, txt_embeds)
-        elif cfg.do_add_method == 'add':
-            if cfg.do_back_txt:
-                txt_embeds = txt_embeds + zd + zl
-            if cfg.do_front_txt and front_txt is not None:
-                txt_embeds = txt_embeds + z_front
-        elif cfg.do_add_method == 'concat':
-            txt_embeds = self.concat_linear(torch.cat((txt_embeds, zd, zl), -1))
-        return self.z_concat_layernorm(txt_embeds)
-
-
-class CausalImageEmbeddings(nn.Module):
-    """M/models/vilmodel_GOAT.py:164-316: R2R/RxR branch and the REVERIE/SOON branch (object tokens appended to the
-    panorama, M:693-720)."""
-
-    def __init__(self, config):
-        super().__init__()
-        self.config = config
-        self.reverie = config.name in ('REVERIE', 'SOON')
-        H = config.hidden_size
-        self.img_linear = Linear(config.image_feat_size, H)
-        self.img_layer_norm = BertLayerNorm(H, eps=1e-12)
-        self.loc_linear = Linear(config.angle_feat_size + 3, H)
-        self.loc_layer_norm = BertLayerNorm(H, eps=1e-12)
-        if not self.reverie:
-            self.img_self_encoder = create_transformer_encoder(config, config.num_pano_layers, norm=True)
-        self.do_back_img = config.do_back_img
-        if self.do_back_img:
-            self.do_img_before_linear = Linear(config.image_feat_size, H)
-            self.do_img_layer_norm = BertLayerNorm(H, eps=1e-12)
-            self.do_img_attn = BertAttention(config)
-            self.do_img_after_linear = Linear(H, H)
-            self.img_after_linear = Linear(H, H)
-            self.do_img_concat_layernorm = BertLayerNorm(H, eps=1e-12)
-            if config.do_back_img_type == 'type_2':
-                if config.do_add_method == 'door':
-                    self.sigmoid = nn.Sigmoid()
-                elif config.do_add_method == 'concat':
-                    self.do_concat_img_linear = Linear(H * 2, H)
-        if self.reverie:
-            if config.use_obj_name:
-                self.obj_name_linear = nn.Embedding(config.obj_name_vocab_size, H)
-            self.obj_reverie_linear = Linear(config.obj_feat_size, H)
-            self.obj_reverie_layer_norm = BertLayerNorm(H, eps=1e-12)
-            self.nav_type_embedding = nn.Embedding(3, H)
-            self.pano_encoder = create_transformer_encoder(config, config.num_pano_layers, norm=True)
-        else:
-            self.nav_type_embedding = nn.Embedding(2, H)
-        if config.adaptive_pano_fusion:
-            self.adaptive_pano_attn = Linear(H, 1)
-        self.layer_norm = BertLayerNorm(H, eps=1e-12)
-        self.dropout = nn.Dropout(config.hidden_dropout_prob)
-
-    def intervene(self, x, z_img_features, z_img_pzs):
-        """BACL-img (M/models/vilmodel_GOAT.py:659-681)."""
-        cfg = self.config
-        dt = x.dtype
-        z = self.do_img_layer_norm(self.do_img_before_linear(z_img_features.to(dt)))
-        if cfg.do_back_img_type == 'type_1':
-            s = hipops.dict_weighted_sum(z, z_img_pzs, dt)
-            x = self.img_after_linear(x) + self.do_img_after_linear(s)
-        else:
-            z = self.do_img_attn(x, None, z, None)
-            if cfg.do_add_method == 'door':
-                w = torch.sigmoid(self.img_after_linear(x).float() + self.do_img_after_linear(z).float()).to(dt)
-                x = w * x + (1 - w) * z
-            elif cfg.do_add_method == 'add':
-                x = x + z
-            elif cfg.do_add_method == 'concat':
-                x = self.do_concat_img_linear(torch.cat((x, z), -1))
-        return self.do_img_concat_layernorm(x)
-
-    def encode(self, view_img_fts, loc_fts, view_lens, z_img_features=None, z_img_pzs=None, loc_before=False,
-               nav_types=None, obj_fts=None, obj_lens=None, obj_names=None, obj_concat=None):
-        """-> (embeds [N,W,H], masks [N,W] bool, fused [N,H] | None).  `loc_before` = pre-training order
-        (location added before the intervention, M:225-252); per-step navigation adds it after (M:688-691).
-        REVERIE/SOON (M:693-720): object tokens follow the views of every row; loc_fts / nav_types are [N,W,...]."""
-        dt = compute_dtype()
-        x = self.img_layer_norm(self.img_linear(view_img_fts.to(dt)))
-        if self.reverie:
-            if z_img_features is not None:
-                x = self.intervene(x, z_img_features, z_img_pzs)
-            o = self.obj_reverie_linear(obj_fts.to(dt))
-            if self.config.use_obj_name:
-                o = o + hipops.embedding(obj_names, self.obj_name_linear.weight, out_dtype=dt)
-            o = self.obj_reverie_layer_norm(o)
-            N, V, H = x.shape
-            W = nav_types.shape[1]
-            src = torch.cat([x.reshape(N * V, H), o.reshape(-1, H)], 0)
-            if obj_concat is not None:      # (idx, start, inv_idx, inv_start) already on the device: shape-stable callers (captured episodes:
-                x = hipops.gather_segmean(src, obj_concat[0], obj_concat[1], None, N * W, tuple(obj_concat[2:4])).view(N, W, H)      # no host read of the lengths)
-            else:
-                ci = graphmap.build_obj_concat_index(view_lens, obj_lens, V, o.shape[1], W)
-                x = hipops.gather_segmean(src, ci[0].to(x.device), ci[1].to(x.device), None, N * W).view(N, W, H)
-            x = x + self.loc_layer_norm(self.loc_linear(loc_fts.to(dt))) \
-                + hipops.embedding(nav_types, self.nav_type_embedding.weight, out_dtype=dt)
-            x = self.layer_norm(x, p_out=_p(self.dropout))
-            masks = gen_seq_masks(view_lens + obj_lens, W)
-            x = self.pano_encoder(x, masks)
-        else:
-            loc_in = self.loc_linear(loc_fts.to(dt))
-            if loc_before:
-                x = x + self.loc_layer_norm(loc_in)
-            if z_img_features is not None:
-                x = self.intervene(x, z_img_features, z_img_pzs)
-            if not loc_before:       # dropout(x + loc_LN(...)): the sum and the dropout inside the LayerNorm's launch
-                x = self.loc_layer_norm(loc_in, post_add=x, p_out=_p(self.dropout))
-            else:
-                x = hipops.dropout(x, _p(self.dropout))
-            masks = gen_seq_masks(view_lens, view_img_fts.shape[1])
-            x = self.img_self_encoder(x, masks)
-        fused = None
-        if self.config.adaptive_pano_fusion:
-            fused = hipops.pano_fusion(x, self.adaptive_pano_attn.weight, self.adaptive_pano_attn.bias)
-        return x, masks, fused
-
-
-class LocalVPEncoder(nn.Module):
-    def __init__(self, config):
-        super().__init__()
-        self.vp_pos_embeddings = nn.Sequential(Linear(config.angle_feat_size * 2 + 6, config.hidden_size),
-                                               BertLayerNorm(config.hidden_size, eps=1e-12))
-        self.encoder = CrossmodalEncoder(config, with_lang_branch=False)
-        if config.mode == 'extract_cfp_features':
-            self.tim_self_encoder = BertAttention(config)
-
-
-class GlobalMapEncoder(nn.Module):
-    def __init__(self, config):
-        super().__init__()
-        self.config = config
-        self.gmap_pos_embeddings = nn.Sequential(Linear(config.angle_feat_size + 3, config.hidden_size),
-                                                 BertLayerNorm(config.hidden_size, eps=1e-12))
-        self.gmap_step_embeddings = nn.Embedding(config.max_action_steps, config.hidden_size)
-        self.encoder = CrossmodalEncoder(config, with_lang_branch=False)
-        self.sprel_linear = Linear(1, 1) if config.graph_sprels else None
-        if config.mode == 'extract_cfp_features':
-            self.tim_self_encoder = BertAttention(config)
 
 
 class FrontDoorEncoder(nn.Module):
@@ -283,10 +49,10 @@ class GlocalTextPathNavCMT(GoatPreTrainedModel):
         super().__init__(config)
         H = config.hidden_size
         self.embeddings = RobertaEmbeddings(config)
-        self.lang_encoder = LanguageEncoderDo(config) if (config.do_back_txt or config.do_front_txt) else LanguageEncoder(config)
-        self.img_embeddings = CausalImageEmbeddings(config)
-        self.local_encoder = LocalVPEncoder(config)
-        self.global_encoder = GlobalMapEncoder(config)
+        self.lang_encoder = LanguageEncoderDo(config, 'nav') if (config.do_back_txt or config.do_front_txt) else LanguageEncoder(config)
+        self.img_embeddings = CausalImageEmbeddings(config, 'nav')
+        self.local_encoder = LocalVPEncoder(config, 'nav')
+        self.global_encoder = GlobalMapEncoder(config, 'nav')
         self.global_sap_head = ClsPrediction(H)
         self.local_sap_head = ClsPrediction(H)
         self.sap_fuse_linear = ClsPrediction(H, input_size=H * 2) if config.glocal_fuse else None
@@ -333,7 +99,7 @@ class GlocalTextPathNavCMT(GoatPreTrainedModel):
     # ---- language ---------------------------------------------------------------------------------
     def forward_text(self, txt_ids, txt_masks, z_direc=None, z_direc_pzs=None, z_landm=None, z_landm_pzs=None, front_txt=None):
         e = self.embeddings(txt_ids)
-        return self.lang_encoder(e, txt_masks, z_direc, z_direc_pzs, z_landm, z_landm_pzs, front_txt)
+        return self.lang_encoder(e, neg_mask(txt_masks), z_direc, z_direc_pzs, z_landm, z_landm_pzs, front_txt)
 
     # ---- panorama -------------------------------------------------------------------------------------
     def forward_panorama_do_per_step(self, view_img_fts, loc_fts, nav_types, view_lens, z_img_features=None, z_img_pzs=None,
@@ -362,9 +128,7 @@ class GlocalTextPathNavCMT(GoatPreTrainedModel):
         # (image embedding + step embedding) + LayerNorm(Linear(position features)): the second sum rides in the LayerNorm launch (post_add)
         ie = gmap_img_embeds.to(dt) + hipops.embedding(gmap_step_ids, ge.gmap_step_embeddings.weight, out_dtype=dt)
         gmap = ge.gmap_pos_embeddings[1](ge.gmap_pos_embeddings[0](gmap_pos_fts.to(dt)), post_add=ie)
-        bias = None
-        if ge.sprel_linear is not None:
-            bias = gmap_pair_dists.float() * ge.sprel_linear.weight.view(()) + ge.sprel_linear.bias.view(())
+        bias = ge.sprels(gmap_pair_dists) if ge.sprel_linear is not None else None
         # the global-map branch (FACL front-door block, cross-modal encoder, its action head and pooler) is independent of the local
         # one until the logit fusion: a parallel branch of the captured step / episode graph, as in the pre-training model
         # (hipops.Branch; both chains are launch-latency-bound at 12 x 60 / 12 x 38 rows)
@@ -425,22 +189,13 @@ class GlocalTextPathNavCMT(GoatPreTrainedModel):
         N, V, H = x.shape
         rows = x.view(N * V, H)
         src = torch.cat([rows, fused], 0) if fused is not None else rows
-        dev = x.device
-        lens_cpu = batch['traj_vp_view_lens'].cpu()
-        G = batch['gmap_step_ids'].shape[1]
-        gi = graphmap.build_gmap_index(batch['traj_step_lens'], lens_cpu, batch['traj_vpids'], batch['traj_cand_vpids'],
-                                       batch['gmap_vpids'], G, V, fused is not None)
-        vi = graphmap.build_vp_index(batch['traj_step_lens'], lens_cpu, V)
-        B = batch['gmap_step_ids'].shape[0]
+        # (no inverse indices: nothing is differentiated here, the pass only fills the FACL dictionaries)
+        idx = trajectory_indices(batch, fused is not None, inverse=False)
         ge, le = self.global_encoder, self.local_encoder
-        gimg = hipops.gather_segmean(src, gi[0].to(dev), gi[1].to(dev), gi[2].to(dev), B * G).view(B, G, H)
-        gmap = gimg + hipops.embedding(batch['gmap_step_ids'], ge.gmap_step_embeddings.weight, out_dtype=x.dtype) \
-            + ge.gmap_pos_embeddings[1](ge.gmap_pos_embeddings[0](batch['gmap_pos_fts'].to(x.dtype)))
-        gmap = ge.tim_self_encoder(gmap, neg_mask(gen_seq_masks(batch['gmap_lens'], G)))
-        W = vi[3]
-        vimg = hipops.gather_segmean(x, vi[0].to(dev), vi[1].to(dev), None, B * W).view(B, W, H)
-        vp = vimg + le.vp_pos_embeddings[1](le.vp_pos_embeddings[0](batch['vp_pos_fts'][:, :W].to(x.dtype)))
-        vp = le.tim_self_encoder(vp, neg_mask(gen_seq_masks(vi[2].to(dev), W)))
+        gmap, gm = ge.gmap_input_embedding(src, idx['gmap'], batch['gmap_step_ids'], batch['gmap_pos_fts'], batch['gmap_lens'])
+        gmap = ge.tim_self_encoder(gmap, neg_mask(gm))
+        vp, vm = le.vp_input_embedding(x, idx['vp'], batch['vp_pos_fts'])
+        vp = le.tim_self_encoder(vp, neg_mask(vm))
         gmap, vp, txt = self.tim_global_head(gmap), self.tim_local_head(vp), self.tim_txt_head(txt)
         return {'txt_outputs': attn_pool(txt, self.tim_txt_attn), 'vp_outputs': attn_pool(vp, self.tim_local_attn),
                 'gmap_outputs': attn_pool(gmap, self.tim_global_attn)}

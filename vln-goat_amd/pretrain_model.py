@@ -14,9 +14,10 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import graphmap, hipops
-from .layers import (BertAttention, BertLayerNorm, BertOnlyMLMHead, BertPredictionHeadTransform, ClsPrediction,
-                     CrossmodalEncoder, LayerNorm, Linear, RegionClassification, RobertaEmbeddings, RobertaLayer, _p, compute_dtype, project_kv_bank,
-                     create_transformer_encoder, gen_seq_masks, neg_mask)
+from .encoders import (CausalImageEmbeddings, GlobalMapEncoder, LanguageEncoder, LanguageEncoderDo, LocalVPEncoder, _door,  # noqa: F401
+                       trajectory_indices)
+from .layers import (BertOnlyMLMHead, BertPredictionHeadTransform, ClsPrediction, RegionClassification, RobertaEmbeddings,
+                     gen_seq_masks, neg_mask, project_kv_bank)
 
 
 class GoatPreTrainedModel(nn.Module):
@@ -77,227 +78,14 @@ class GoatPreTrainedModel(nn.Module):
         return model
 
 
-def _cfg(config, name, default):
-    v = getattr(config, name, default)
-    return default if v is None else v
-
-
-class LanguageEncoder(nn.Module):
-    # P/model/vilmodel_goat.py:24-44
-    def __init__(self, config):
-        super().__init__()
-        self.num_l_layers = config.num_l_layers
-        self.update_lang_bert = config.update_lang_bert
-        self.layer = nn.ModuleList([RobertaLayer(config) for _ in range(self.num_l_layers)])
-        if not self.update_lang_bert:
-            for _, param in self.layer.named_parameters():
-                param.requires_grad = False
-
-    def forward(self, txt_embeds, txt_kmask):
-        for i, layer in enumerate(self.layer):       # between layers the state travels as a layers._pair (fork=True)
-            txt_embeds = layer(txt_embeds, txt_kmask, fork=i + 1 < len(self.layer))
-        if not self.update_lang_bert:
-            txt_embeds = txt_embeds.detach()
-        return txt_embeds
-
-
-def _door(aug_lin, ori_lin, aug, ori):
-    """door gate: w = sigmoid(Linear_a(aug) + Linear_o(ori)); out = w*aug + (1-w)*ori (P/model/vilmodel_goat.py:137-143)."""
-    return hipops.door_gate(aug_lin, ori_lin, aug, ori)
-
-
-class LanguageEncoderDo(nn.Module):
-    """BACL-txt in pre-training (P/model/vilmodel_goat.py:46-159): after the RoBERTa layers the text is intervened
-    with the direction / landmark confounder dictionaries — type_1: probability-weighted dictionary sums through
-    three Linears (optionally dictionary->text cross-attention first, z_cross_attn); type_2: text->dictionary
-    cross-attention, then door / add / concat — followed by LayerNorm.  Module set mirrors the reference's
-    constructor (state_dict keys), including modules it creates and never calls (txt_self_attn, z_front_*)."""
-
-    def __init__(self, config):
-        super().__init__()
-        self.config = config
-        self.num_l_layers = config.num_l_layers
-        self.update_lang_bert = config.update_lang_bert
-        self.layer = nn.ModuleList([RobertaLayer(config) for _ in range(self.num_l_layers)])
-        if not self.update_lang_bert:
-            for _, param in self.layer.named_parameters():
-                param.requires_grad = False
-        H = config.hidden_size
-        if config.do_back_txt:
-            if config.z_cross_attn:
-                self.z_direc_cross_attn = BertAttention(config)
-                self.z_landm_cross_attn = BertAttention(config)
-            self.z_txt_linear = Linear(H, H)
-            self.z_direct_linear = Linear(H, H)
-            self.z_landm_linear = Linear(H, H)
-            self.z_concat_layernorm = BertLayerNorm(H, eps=config.layer_norm_eps)
-            self.z_direct_ln = BertLayerNorm(H, eps=config.layer_norm_eps)
-            self.z_landm_ln = BertLayerNorm(H, eps=config.layer_norm_eps)
-            if config.do_back_txt_type == 'type_2':
-                self.z_direc_cross_attn = BertAttention(config)
-                self.z_landm_cross_attn = BertAttention(config)
-                self.txt_self_attn = BertAttention(config)
-                self.instr_aug_linear = Linear(H, 1)
-                self.instr_ori_linear = Linear(H, 1)
-                self.instr_sigmoid = nn.Sigmoid()
-                self.concat_linear = Linear(H * 3, H)
-        if getattr(config, 'do_front_txt', False):
-            self.z_front_cross_attn = BertAttention(config)
-            self.z_front_linear = Linear(H, H)
-            self.z_front_ln = BertLayerNorm(H, eps=config.layer_norm_eps)
-        self.dropout = nn.Dropout(config.hidden_dropout_prob)
-
-    def forward(self, txt_embeds, txt_kmask, z_direc=None, z_direc_pzs=None, z_landm=None, z_landm_pzs=None):
-        cfg = self.config
-        for i, layer in enumerate(self.layer):       # between layers the state travels as a layers._pair (fork=True)
-            txt_embeds = layer(txt_embeds, txt_kmask, fork=i + 1 < len(self.layer))
-        if not self.update_lang_bert:
-            txt_embeds = txt_embeds.detach()
-        if z_direc is None:
-            return txt_embeds
-        dt = txt_embeds.dtype
-        z_direc, z_landm = z_direc.to(dt), (z_landm.to(dt) if z_landm is not None else None)
-        if cfg.do_back_txt_type == 'type_1':
-            if cfg.z_cross_attn:       # dictionary entries attend to the (key-masked) text
-                z_direc = self.z_direc_cross_attn(z_direc, None, txt_embeds, txt_kmask)
-                z_landm = self.z_landm_cross_attn(z_landm, None, txt_embeds, txt_kmask)
-            sd = hipops.dict_weighted_sum(z_direc, z_direc_pzs, dt)
-            sl = hipops.dict_weighted_sum(z_landm, z_landm_pzs, dt)
-            txt_embeds = self.z_txt_linear(txt_embeds) + self.z_direct_linear(sd) + self.z_landm_linear(sl)
-            return self.z_concat_layernorm(txt_embeds)
-        # type_2: the text attends to each dictionary (no key mask on dictionary entries)
-        zd = self.z_direct_ln(self.z_direct_linear(self.z_direc_cross_attn(txt_embeds, None, z_direc, None)))
-        zl = None
-        if z_landm is not None:
-            zl = self.z_landm_ln(self.z_landm_linear(self.z_landm_cross_attn(txt_embeds, None, z_landm, None)))
-        if cfg.do_add_method == 'door':
-            aug = zd if zl is None else zd + zl
-            txt_embeds = _door(self.instr_aug_linear, self.instr_ori_linear, aug, txt_embeds)
-        elif cfg.do_add_method == 'add':
-            txt_embeds = txt_embeds + zd + zl
-        elif cfg.do_add_method == 'concat':
-            txt_embeds = self.concat_linear(torch.cat((txt_embeds, zd, zl), -1))
-        return self.z_concat_layernorm(txt_embeds)
-
-
-class CausalImageEmbeddings(nn.Module):
-    """P/model/vilmodel_goat.py:234-364: the R2R branch (view + location embeddings through the panorama encoder)
-    and the REVERIE/SOON branch (object tokens appended to every panorama, :322-349).  Shipped pre-train configs
-    keep do_back_img off — the upstream BACL-img pretrain branch is broken, SURVEY §8a-Q viii."""
-
-    def __init__(self, config):
-        super().__init__()
-        self.config = config
-        self.reverie = getattr(config, 'name', 'R2R') in ('REVERIE', 'SOON')
-        if getattr(config, 'do_back_img', False):
-            raise NotImplementedError('pretrain do_back_img is broken upstream (undefined do_back_img_after_linear)')
-        H = config.hidden_size
-        self.img_linear = Linear(config.image_feat_size, H)
-        self.img_layer_norm = BertLayerNorm(H, eps=1e-12)
-        self.loc_linear = Linear(config.angle_feat_size + 3, H)
-        self.loc_layer_norm = BertLayerNorm(H, eps=1e-12)
-        if not self.reverie:
-            self.img_self_attn = BertAttention(config)          # created, never used (checkpoint compat)
-            self.img_self_encoder = create_transformer_encoder(config, config.num_pano_layers, norm=True)
-        if self.reverie:
-            self.obj_name_linear = nn.Embedding(config.obj_name_vocab_size, H)
-            self.obj_reverie_linear = Linear(config.obj_feat_size, H)
-            self.obj_reverie_layer_norm = BertLayerNorm(H, eps=1e-12)
-            self.nav_type_embedding = nn.Embedding(3, H)
-            self.pano_encoder = create_transformer_encoder(config, config.num_pano_layers, norm=True)
-        else:
-            self.nav_type_embedding = nn.Embedding(2, H)    # unused on R2R
-        if config.adaptive_pano_fusion:
-            self.adaptive_pano_attn = Linear(H, 1)
-        self.layer_norm = BertLayerNorm(H, eps=1e-12)       # unused on R2R
-        self.dropout = nn.Dropout(config.hidden_dropout_prob)
-
-    def forward(self, traj_view_img_fts, traj_loc_fts, traj_vp_view_lens, traj_nav_types=None, obj_fts=None, obj_lens=None,
-                obj_names=None, cat_index=None, cat_inverse=None):
-        """-> (tokens [N,W,H], fused [N,H] | None).  cat_index = graphmap.build_obj_concat_index(...) on device (cat_inverse: its
-        graphmap.inverse_index, optional)."""
-        dt = compute_dtype()
-        x = self.img_layer_norm(self.img_linear(traj_view_img_fts.to(dt)))
-        if not self.reverie:
-            # dropout(img_LN(...) + loc_LN(...)): the sum and the dropout inside the second LayerNorm's launch
-            x = self.loc_layer_norm(self.loc_linear(traj_loc_fts.to(dt)), post_add=x, p_out=_p(self.dropout))
-            img_masks = gen_seq_masks(traj_vp_view_lens, traj_view_img_fts.shape[1])
-            x = self.img_self_encoder(x, img_masks)
-        if obj_fts is not None:
-            o = self.obj_reverie_linear(obj_fts.to(dt))
-            if self.config.use_obj_name:
-                o = o + hipops.embedding(obj_names, self.obj_name_linear.weight, out_dtype=dt)
-            o = self.obj_reverie_layer_norm(o)
-            N, V, H = x.shape
-            W = traj_nav_types.shape[1]
-            src = torch.cat([x.reshape(N * V, H), o.reshape(-1, H)], 0)
-            x = hipops.gather_segmean(src, cat_index[0], cat_index[1], None, N * W, cat_inverse).view(N, W, H)
-            x = x + hipops.embedding(traj_nav_types, self.nav_type_embedding.weight, out_dtype=dt) \
-                + self.loc_layer_norm(self.loc_linear(traj_loc_fts.to(dt)))
-            x = self.layer_norm(x, p_out=_p(self.dropout))
-            x = self.pano_encoder(x, gen_seq_masks(traj_vp_view_lens + obj_lens, W))
-        fused = None
-        if self.config.adaptive_pano_fusion:
-            fused = hipops.pano_fusion(x, self.adaptive_pano_attn.weight, self.adaptive_pano_attn.bias)
-        return x, fused
-
-
-class LocalVPEncoder(nn.Module):
-    # P/model/vilmodel_goat.py:366-410
-    def __init__(self, config):
-        super().__init__()
-        self.vp_pos_embeddings = nn.Sequential(Linear(config.angle_feat_size * 2 + 6, config.hidden_size),
-                                               BertLayerNorm(config.hidden_size, eps=1e-12))
-        self.encoder = CrossmodalEncoder(config)
-        if 'cfp' in config.pretrain_tasks:
-            self.tim_self_encoder = BertAttention(config)
-
-    def vp_input_embedding(self, pano_embeds, idx, vp_pos_fts, inverse=None):
-        """pano_embeds [N,V,H]; idx = graphmap.build_vp_index(...) on device (inverse: its graphmap.inverse_index, optional)."""
-        vidx, vstart, vp_lens, width = idx
-        B = vp_pos_fts.shape[0]
-        vp_img = hipops.gather_segmean(pano_embeds, vidx, vstart, None, B * width, inverse).view(B, width, -1)
-        # (kept as a separate add: folding it into the LayerNorm launch (post_add) removes one bf16 rounding, which moved the most
-        #  noise-sensitive gradient of the model — sap_fuse_linear, a difference of two softmax-weighted sums — past its calibrated
-        #  bf16 bound in 2 of 16 parity cases; 3 us per step are not worth re-calibrating the bound)
-        pos = self.vp_pos_embeddings[1](self.vp_pos_embeddings[0](vp_pos_fts[:, :width].to(vp_img.dtype)))
-        return vp_img + pos, gen_seq_masks(vp_lens, width)
-
-
-class GlobalMapEncoder(nn.Module):
-    # P/model/vilmodel_goat.py:412-527
-    def __init__(self, config):
-        super().__init__()
-        self.gmap_pos_embeddings = nn.Sequential(Linear(config.angle_feat_size + 3, config.hidden_size),
-                                                 BertLayerNorm(config.hidden_size, eps=1e-12))
-        self.gmap_step_embeddings = nn.Embedding(config.max_action_steps, config.hidden_size)
-        self.encoder = CrossmodalEncoder(config)
-        if 'cfp' in config.pretrain_tasks:
-            self.tim_self_encoder = BertAttention(config)
-        self.sprel_linear = Linear(1, 1) if config.graph_sprels else None
-
-    def gmap_input_embedding(self, src_rows, idx, gmap_step_ids, gmap_pos_fts, gmap_lens, inverse=None):
-        gidx, gstart, gscale = idx
-        B, G = gmap_step_ids.shape
-        img = hipops.gather_segmean(src_rows, gidx, gstart, gscale, B * G, inverse).view(B, G, -1)
-        pos = self.gmap_pos_embeddings[1](self.gmap_pos_embeddings[0](gmap_pos_fts.to(img.dtype)))
-        e = img + hipops.embedding(gmap_step_ids, self.gmap_step_embeddings.weight, out_dtype=img.dtype) + pos
-        return e, gen_seq_masks(gmap_lens, G)
-
-    def sprels(self, gmap_pair_dists):
-        # Linear(1,1) on the distance matrix (:496-497); float32, gradient flows back through the attention bias
-        w, b = self.sprel_linear.weight.view(()), self.sprel_linear.bias.view(())
-        return gmap_pair_dists.float() * w + b
-
-
 class GlocalTextPathCMT(GoatPreTrainedModel):
     def __init__(self, config):
         super().__init__(config)
         self.embeddings = RobertaEmbeddings(config)
-        self.lang_encoder = LanguageEncoderDo(config) if getattr(config, 'do_back_txt', False) else LanguageEncoder(config)
-        self.img_embeddings = CausalImageEmbeddings(config)
-        self.local_encoder = LocalVPEncoder(config)
-        self.global_encoder = GlobalMapEncoder(config)
+        self.lang_encoder = LanguageEncoderDo(config, 'pretrain') if getattr(config, 'do_back_txt', False) else LanguageEncoder(config)
+        self.img_embeddings = CausalImageEmbeddings(config, 'pretrain')
+        self.local_encoder = LocalVPEncoder(config, 'pretrain')
+        self.global_encoder = GlobalMapEncoder(config, 'pretrain')
         self.init_weights()
 
     # -- shared stems -----------------------------------------------------------------------
@@ -305,33 +93,7 @@ class GlocalTextPathCMT(GoatPreTrainedModel):
         """Per-batch host index tensors, cached on the caller's batch dict."""
         cache = batch.get('_goat_cache')
         if cache is None:
-            dev = batch['traj_view_img_fts'].device
-            V = batch['traj_view_img_fts'].shape[1]
-            G = batch['gmap_step_ids'].shape[1]
-            fused = bool(self.config.adaptive_pano_fusion)
-            lens_cpu = batch['traj_vp_view_lens'].cpu()
-            cache = {}
-            if batch.get('traj_obj_img_fts') is not None:
-                # REVERIE/SOON: every panorama row becomes [views | objects], W slots wide (P/model/vilmodel_goat.py:331-341)
-                obj_cpu = batch['traj_vp_obj_lens'].cpu()
-                W = batch['traj_nav_types'].shape[1]
-                ci = graphmap.build_obj_concat_index(lens_cpu, obj_cpu, V, batch['traj_obj_img_fts'].shape[1], W)
-                cache['objcat'] = (ci[0].to(dev), ci[1].to(dev))
-                n_rows = int(lens_cpu.shape[0])
-                cache['objcat_inv'] = tuple(t.to(dev) for t in graphmap.inverse_index(
-                    ci[0], ci[1], None, n_rows * V + n_rows * batch['traj_obj_img_fts'].shape[1]) if t is not None)
-                cache['view_lens_cpu'], cache['obj_lens_cpu'] = lens_cpu, obj_cpu
-                lens_cpu, V = lens_cpu + obj_cpu, W
-            g = graphmap.build_gmap_index(batch['traj_step_lens'], lens_cpu, batch['traj_vpids'],
-                                          batch['traj_cand_vpids'], batch['gmap_vpids'], G, V, fused)
-            v = graphmap.build_vp_index(batch['traj_step_lens'], lens_cpu, V)
-            cache['gmap'] = tuple(t.to(dev) for t in g)
-            cache['vp'] = (v[0].to(dev), v[1].to(dev), v[2].to(dev), v[3])
-            # inverse indices: the backward passes of the two gathers are gathers over the output gradients (no atomics / fills)
-            n_rows = int(lens_cpu.shape[0])
-            cache['gmap_inv'] = tuple(t.to(dev) for t in graphmap.inverse_index(g[0], g[1], g[2], n_rows * V + (n_rows if fused else 0)))
-            cache['vp_inv'] = tuple(t.to(dev) for t in graphmap.inverse_index(v[0], v[1], None, n_rows * V) if t is not None)
-            batch['_goat_cache'] = cache
+            cache = batch['_goat_cache'] = trajectory_indices(batch, bool(self.config.adaptive_pano_fusion))
         return cache
 
     def _text(self, batch):
