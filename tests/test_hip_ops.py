@@ -1540,3 +1540,64 @@ def test_layer_norm_backward_768_kernel_matches_the_generic_kernel(ops, M, form)
         scale = b.abs().max().clamp_min(1e-6)
         assert (a - b).abs().max() / scale < 1e-2, (form, i, float((a - b).abs().max() / scale))       # (a bf16 ulp where a rounding flips)
         assert (a - b).abs().mean() / scale < 2e-5, (form, i, float((a - b).abs().mean() / scale))
+
+
+def test_profile_records_replay_the_launch_they_describe(ops):
+    """tuning.PROFILE holds, per GEMM launch, (start, stop, flops, shape key, (C symbol, its arguments without the stream, tensors
+    kept alive)); bench.py's roofline leg replays `getattr(lib, symbol)(stream, *arguments)` verbatim.  The arguments are the tuple the
+    launch itself was made from: replayed into cleared outputs they must give status 0 and the same bits.  One bf16 launch on
+    goat_gemm_bf16 (bias, GELU epilogue, pre-activation output) and two float32 launches that go through the explicit transpose to
+    goat_gemm_nt with tails in every dimension: K = 12, a whole number of 16-byte chunks, and K = 10, where the transposed operand
+    comes out 12 wide and the other one is zero-padded to match.  There the arguments point at temporaries that only the record keeps
+    alive: same-sized NaN buffers allocated after the launch would take their memory if it had been released."""
+    from vln_goat_amd import _lib, tuning
+    from vln_goat_amd._lib import EPI_GELU, GOAT_BF16
+    g = torch.Generator().manual_seed(21)
+    M, N, Kc = 128, 64, 64
+    a = torch.randn(M, Kc, generator=g).to(DEV, torch.bfloat16)
+    b = (torch.randn(N, Kc, generator=g) * 0.1).to(DEV, torch.bfloat16)
+    bias = torch.randn(N, generator=g).to(DEV)
+    out = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
+    aux = torch.empty_like(out)
+    a32 = torch.randn(5, 12, generator=g).to(DEV)
+    b32 = torch.randn(12, 7, generator=g).to(DEV)
+    out32 = torch.empty(5, 7, device=DEV)
+    a10 = torch.randn(5, 10, generator=g).to(DEV)
+    b10 = torch.randn(10, 7, generator=g).to(DEV)
+    out10 = torch.empty(5, 7, device=DEV)
+    autotune = tuning.AUTOTUNE
+    tuning.AUTOTUNE = False
+    ops.PROFILE = []
+    try:
+        ops.gemm(a, b, out, ta=False, tb=False, bias=bias, epi=EPI_GELU, aux=aux)
+        ops.gemm(a32, b32, out32, tb=True)
+        ops.gemm(a10, b10, out10, tb=True)
+        recs = ops.PROFILE
+    finally:
+        ops.PROFILE = None
+        tuning.AUTOTUNE = autotune
+    torch.cuda.synchronize()
+    junk = [torch.full(shape, float('nan'), device=DEV) for shape in ((5, 12), (7, 12)) for _ in range(8)]
+    assert [r[4][0] for r in recs] == ['goat_gemm_bf16', 'goat_gemm_nt', 'goat_gemm_nt']
+    assert len(recs[0]) == 5 and len(recs[0][4]) == 3
+    c = recs[0][4][1]
+    assert c[2] == GOAT_BF16                                  # dtype_out: bench.py reads r[4][1][2] for the bytes of the output
+    assert (c[3], c[5], c[7], c[12], c[14]) == (a.data_ptr(), b.data_ptr(), out.data_ptr(), bias.data_ptr(), aux.data_ptr())
+    assert recs[0][3][:5] == (M, N, Kc, EPI_GELU, 1) and recs[1][3][:3] == (5, 7, 12) and recs[2][3][:3] == (5, 7, 12)
+    assert recs[1][4][1][2] == a32.data_ptr()                 # K = 12: the left operand goes in as it is
+    assert recs[2][4][1][2] != a10.data_ptr() and recs[2][4][2][0].shape == (5, 12)      # K = 10: a padded copy, kept by the record
+    _close(aux, a.float() @ b.float().T + bias, torch.bfloat16, 'first launch, pre-activation')
+    _close(out32, a32 @ b32, torch.float32, 'first launch, float32')
+    _close(out10, a10 @ b10, torch.float32, 'first launch, float32, padded')
+    L = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    for r, outs in zip(recs, ((out, aux), (out32,), (out10,))):
+        first = [t.clone() for t in outs]
+        for t in outs:
+            t.zero_()
+        name, cargs, _keep = r[4]
+        assert getattr(L, name)(st, *cargs) == 0
+        torch.cuda.synchronize()
+        for t, f in zip(outs, first):
+            assert torch.equal(t, f), '%s: the replay differs from the launch' % name
+    del junk

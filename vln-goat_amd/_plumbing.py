@@ -1,6 +1,8 @@
-"""Pointer / dtype / stream helpers shared by the modules that call the C ABI (hipops, tuning, wgrad_queue)."""
+"""Pointer / dtype / stream helpers and the one launch path into the C ABI, shared by the modules that call it (hipops, tuning,
+wgrad_queue, optim)."""
 import torch
 
+from . import _lib
 from ._lib import GOAT_BF16, GOAT_F32
 
 
@@ -27,3 +29,36 @@ def _need_gpu(t):
 
 def _ptr(t, off=0):
     return t.data_ptr() + off * t.element_size()
+
+
+# The per-argument test of cargs / launch, cheapest case first: plain values by exact type, tensors by exact type, and only then
+# isinstance() (a tensor subclass; ctypes arrays and structs fall through it).  isinstance() against torch.Tensor goes through the
+# tensor metaclass and costs more than everything else in the loop, and the eager step makes several hundred launches.
+_PLAIN = frozenset({int, float, type(None)})
+_TENSOR = frozenset({torch.Tensor, torch.nn.Parameter})
+
+
+def cargs(*args):
+    """The arguments of a C-ABI call as ctypes takes them: a tensor becomes its data pointer; None (a null pointer), ints (a pointer with
+    an element offset is the int `_ptr(t, off)`), floats, ctypes arrays and ctypes structs stay as they are."""
+    return tuple([a if type(a) in _PLAIN else a.data_ptr() if (type(a) in _TENSOR or isinstance(a, torch.Tensor)) else a for a in args])
+
+
+def call(symbol, ctuple, what=None):
+    """launch() for arguments that are converted already (ctuple = cargs(...)): the GEMM wrappers launch from the very tuple they keep
+    in the tuning.PROFILE record."""
+    st = getattr(_lib.lib(), symbol)(_stream(), *ctuple)
+    if st:
+        _lib.check(st, what or symbol)
+
+
+def launch(symbol, *args, what=None):
+    """Run `symbol` of libgoat_hip.so on the current torch stream with cargs(*args); a non-zero status raises, naming `what` (a label
+    with the shapes in it) or the symbol.  Every stream-taking entry point is called through here or through call(), except: the queries
+    that return a value instead of a status (goat_version, goat_ln_bwd_nparts, goat_ln_bwd_ws_floats, goat_wgrad_balanced_ws_bytes), and
+    WgradQueue._run, whose callers want the raw status (the tuner tries configurations the library may reject).
+    (cargs' comprehension is written out here: a nested call per launch costs as much as converting five arguments.)"""
+    st = getattr(_lib.lib(), symbol)(_stream(), *[a if type(a) in _PLAIN else a.data_ptr() if (type(a) in _TENSOR or isinstance(a, torch.Tensor)) else a
+                                                  for a in args])
+    if st:
+        _lib.check(st, what or symbol)

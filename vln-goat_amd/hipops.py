@@ -24,7 +24,7 @@ _ACT_DEPI = {'gelu': EPI_MUL_DGELU, 'relu': EPI_MUL_DRELU}
 
 
 # ----------------------------------------------------------------------------- plumbing
-from ._plumbing import _dt, _epc, _need_gpu, _ptr, _stream          # noqa: E402,F401
+from ._plumbing import _dt, _epc, _need_gpu, _ptr, _stream, call, cargs, launch          # noqa: E402,F401
 
 
 class RngState:
@@ -74,18 +74,12 @@ def gemm_nt(a, b, out, bias=None, epi=EPI_NONE, aux=None, split_k=1):
     N = b.shape[0]
     assert b.shape[1] == K and out.shape[0] == M and out.shape[1] == N
     ev = _profile_start() if tuning.PROFILE is not None else None
-    st = _lib.lib().goat_gemm_nt(_stream(), _dt(a), _dt(out), _ptr(a), a.stride(0), _ptr(b), b.stride(0),
-                                 _ptr(out), out.stride(0), M, N, K,
-                                 _ptr(bias) if bias is not None else None, epi,
-                                 _ptr(aux) if aux is not None else None,
-                                 aux.stride(0) if aux is not None else 0, split_k)
-    _lib.check(st, 'goat_gemm_nt(M=%d,N=%d,K=%d)' % (M, N, K))
+    args = cargs(_dt(a), _dt(out), a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, K, bias, epi, aux,
+                 aux.stride(0) if aux is not None else 0, split_k)
+    call('goat_gemm_nt', args, what='goat_gemm_nt(M=%d,N=%d,K=%d)' % (M, N, K))
     if ev is not None:
         ev[1].record()
-        cargs = (_dt(a), _dt(out), _ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(out), out.stride(0), M, N, K,
-                 _ptr(bias) if bias is not None else None, epi, _ptr(aux) if aux is not None else None,
-                 aux.stride(0) if aux is not None else 0, split_k)
-        tuning.PROFILE.append(ev + (2.0 * M * N * K, (M, N, K, epi, split_k, str(a.dtype)), ('goat_gemm_nt', cargs, (a, b, out, bias, aux))))
+        tuning.PROFILE.append(ev + (2.0 * M * N * K, (M, N, K, epi, split_k, str(a.dtype)), ('goat_gemm_nt', args, (a, b, out, bias, aux))))
     return out
 
 
@@ -95,9 +89,7 @@ def transpose_pad(x, colsum=None):
     e = _epc(x)
     ld = (R + e - 1) // e * e
     out = torch.empty((C, ld), dtype=x.dtype, device=x.device)
-    st = _lib.lib().goat_transpose(_stream(), _dt(x), _ptr(x), x.stride(0), _ptr(out), ld, R, C,
-                                   _ptr(colsum) if colsum is not None else None)
-    _lib.check(st, 'goat_transpose')
+    launch('goat_transpose', _dt(x), x, x.stride(0), out, ld, R, C, colsum)
     return out
 
 
@@ -110,8 +102,7 @@ def colsum(x, out=None):
     R, C = x.shape
     if out is None:
         out = torch.zeros(C, dtype=torch.float32, device=x.device)
-    st = _lib.lib().goat_colsum(_stream(), _dt(x), _ptr(x), x.stride(0), R, C, _ptr(out))
-    _lib.check(st, 'goat_colsum')
+    launch('goat_colsum', _dt(x), x, x.stride(0), R, C, out)
     return out
 
 
@@ -193,15 +184,11 @@ def gemm(a, b, out, ta=False, tb=False, bias=None, epi=EPI_NONE, aux=None, split
         assert epi == EPI_NONE and out.dtype == torch.float32 and bias is None
         epi = EPI_ACCUM
     ev = _profile_start() if tuning.PROFILE is not None else None
-    _launch_gemm_bf16(a, b, out, ta, tb, M, N, Kc, bias, epi, aux, split_k, bm, nstage, colsum_out)
+    args = _launch_gemm_bf16(a, b, out, ta, tb, M, N, Kc, bias, epi, aux, split_k, bm, nstage, colsum_out)
     if ev is not None:
         ev[1].record()
-        cargs = (int(ta), int(tb), _dt(out), _ptr(a), a.stride(0), _ptr(b), b.stride(0), _ptr(out),
-                 out.stride(0), M, N, Kc, _ptr(bias) if bias is not None else None, epi,
-                 _ptr(aux) if aux is not None else None, aux.stride(0) if aux is not None else 0,
-                 split_k, bm, nstage, _ptr(colsum_out) if colsum_out is not None else None)
         tuning.PROFILE.append(ev + (2.0 * M * N * Kc, (M, N, Kc, epi, split_k, 'v2 t%d%d %s %s' % (ta, tb, tile_name(bm), stage_name(nstage))),
-                                    ('goat_gemm_bf16', cargs, (a, b, out, bias, aux, colsum_out))))
+                                    ('goat_gemm_bf16', args, (a, b, out, bias, aux, colsum_out))))
     return out
 
 
@@ -292,7 +279,7 @@ def _rows(x, dtype=None):
     x2 = x.reshape(-1, x.shape[-1])
     if dtype is not None and x2.dtype != dtype:
         x2 = x2.to(dtype)
-    return x2 if x2.is_contiguous() else x2.contiguous()
+    return x2.contiguous()
 
 
 def _pad_k(x, e):
@@ -366,9 +353,7 @@ class _LinearFn(torch.autograd.Function):
             else:
                 dwt = torch.zeros(weight.shape, dtype=torch.float32, device=dy2.device)
                 dbt = torch.zeros(weight.shape[0], dtype=torch.float32, device=dy2.device) if ctx.has_bias else None
-            st = _lib.lib().goat_wgrad_smallk(_stream(), _dt(dy2), _ptr(dy2), dy2.stride(0), _ptr(x2), x2.stride(0), dy2.shape[0],
-                                              dy2.shape[1], K, _ptr(dwt), dwt.stride(0), _ptr(dbt) if dbt is not None else None)
-            _lib.check(st, 'goat_wgrad_smallk')
+            launch('goat_wgrad_smallk', _dt(dy2), dy2, dy2.stride(0), x2, x2.stride(0), dy2.shape[0], dy2.shape[1], K, dwt, dwt.stride(0), dbt)
             if sinks is None:
                 dw, db = dwt, dbt
         elif ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
@@ -391,8 +376,7 @@ class _RowDotFn(torch.autograd.Function):
         x2 = _rows(x)
         M, H = x2.shape
         y = torch.empty(M, dtype=x2.dtype, device=x2.device)
-        st = _lib.lib().goat_rowdot_fwd(_stream(), _dt(x2), _ptr(x2), _ptr(weight), _ptr(bias) if bias is not None else None, _ptr(y), M, H)
-        _lib.check(st, 'goat_rowdot_fwd')
+        launch('goat_rowdot_fwd', _dt(x2), x2, weight, bias, y, M, H)
         ctx.save_for_backward(x2)
         ctx.weight, ctx.bias, ctx.xshape = weight, bias, x.shape
         return y.view(*x.shape[:-1], 1)
@@ -405,8 +389,7 @@ class _RowDotFn(torch.autograd.Function):
         dy2 = dy.reshape(-1)
         if dy2.dtype != x2.dtype:
             dy2 = dy2.to(x2.dtype)
-        if not dy2.is_contiguous():
-            dy2 = dy2.contiguous()
+        dy2 = dy2.contiguous()
         dx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
         need_w = ctx.needs_input_grad[1] or (bias is not None and ctx.needs_input_grad[2])
         dw = db = dwt = dbt = None
@@ -418,9 +401,7 @@ class _RowDotFn(torch.autograd.Function):
                 buf = torch.zeros(H + 1, dtype=torch.float32, device=x2.device)
                 dwt, dbt = buf[:H], (buf[H:] if bias is not None else None)
                 dw, db = dwt.view(weight.shape), (dbt.view(bias.shape) if bias is not None else None)
-        st = _lib.lib().goat_rowdot_bwd(_stream(), _dt(x2), _ptr(x2), _ptr(weight), _ptr(dy2), _ptr(dx) if dx is not None else None,
-                                        _ptr(dwt) if dwt is not None else None, _ptr(dbt) if dbt is not None else None, M, H)
-        _lib.check(st, 'goat_rowdot_bwd')
+        launch('goat_rowdot_bwd', _dt(x2), x2, weight, dy2, dx, dwt, dbt, M, H)
         return (dx.view(ctx.xshape) if dx is not None else None), dw, db
 
 
@@ -437,11 +418,9 @@ def linear(x, weight, bias=None, act=None, out_dtype=None):
 
 def act_bwd(dy, u, act, p=0.0, rng=(0, 0, None)):
     """dx = dropmask_p(dy) * act'(u)  (goat_act_bwd)."""
-    dy = dy if dy.is_contiguous() else dy.contiguous()
+    dy = dy.contiguous()
     dx = torch.empty_like(dy)
-    st = _lib.lib().goat_act_bwd(_stream(), _dt(dy), _ptr(dy), _ptr(u), _ptr(dx), dy.numel(), _ACT_EPI[act],
-                                 p, rng[0], rng[1], rng[2])
-    _lib.check(st, 'goat_act_bwd')
+    launch('goat_act_bwd', _dt(dy), dy, u, dx, dy.numel(), _ACT_EPI[act], p, rng[0], rng[1], rng[2])
     return dx
 
 
@@ -463,9 +442,7 @@ class _FfnFn(torch.autograd.Function):
         rng = RngState.next(h.numel()) if p > 0 else (0, 0, None)
         gemm(x2, W1, h, bias=b1.detach(), epi=_ACT_EPI[act], aux=u)
         if p > 0:
-            st = _lib.lib().goat_dropout_add_fwd(_stream(), _dt(h), _ptr(h), None, _ptr(h), h.numel(), p,
-                                                 rng[0], rng[1], rng[2])
-            _lib.check(st, 'goat_dropout_add_fwd')
+            launch('goat_dropout_add_fwd', _dt(h), h, None, h, h.numel(), p, rng[0], rng[1], rng[2])
         y = torch.empty((M, W2.shape[0]), dtype=x2.dtype, device=x2.device)
         gemm(h, W2, y, bias=b2.detach())
         ctx.save_for_backward(x2, u, h)
@@ -519,8 +496,7 @@ class _DecoderCeFn(torch.autograd.Function):
         loss = torch.empty(M, dtype=torch.float32, device=h.device)
         lse = torch.empty(M, dtype=torch.float32, device=h.device)
         tg = targets.contiguous()
-        st = _lib.lib().goat_ce_fwd(_stream(), _ptr(logits), Nl, M, N, _ptr(tg), _ptr(loss), _ptr(lse))
-        _lib.check(st, 'goat_ce_fwd')
+        launch('goat_ce_fwd', logits, Nl, M, N, tg, loss, lse)
         ctx.save_for_backward(h2, logits, lse, tg)
         ctx.weight, ctx.bias, ctx.N, ctx.hshape = weight, bias, N, h.shape
         return loss
@@ -533,8 +509,7 @@ class _DecoderCeFn(torch.autograd.Function):
         Nl = logits.shape[1]
         dl = torch.empty((M, Nl), dtype=h2.dtype, device=h2.device)
         dloss = dloss.contiguous().float()
-        st = _lib.lib().goat_ce_bwd(_stream(), _dt(dl), _ptr(logits), Nl, M, N, _ptr(tg), _ptr(lse), _ptr(dloss), _ptr(dl), Nl)
-        _lib.check(st, 'goat_ce_bwd')
+        launch('goat_ce_bwd', _dt(dl), logits, Nl, M, N, tg, lse, dloss, dl, Nl)
         if h2.dtype == torch.bfloat16:
             W = _shadow_rows_padded(weight, h2.dtype, Nl)
             dh32 = torch.zeros((M, K), dtype=torch.float32, device=h2.device)
@@ -731,11 +706,7 @@ class _LnFn(torch.autograd.Function):
         if post_add is not None:             # y = dropout_out(LayerNorm(z) + post_add)
             pa = _rows(post_add, x2.dtype)
         ctx.has_post = pa is not None
-        st = _lib.lib().goat_ln_fwd_do(_stream(), _dt(x2), _ptr(x2), _ptr(r2) if r2 is not None else None,
-                                       _ptr(gamma), _ptr(beta), eps, p, seed, off, dev,
-                                       _ptr(y), _ptr(z) if z is not None else None, _ptr(mean), _ptr(rstd), M, H, p_out, off_out,
-                                       _ptr(pa) if pa is not None else None)
-        _lib.check(st, 'goat_ln_fwd')
+        launch('goat_ln_fwd_do', _dt(x2), x2, r2, gamma, beta, eps, p, seed, off, dev, y, z, mean, rstd, M, H, p_out, off_out, pa)
         ctx.save_for_backward(z if z is not None else x2, gamma, mean, rstd)
         ctx.rng = (p, seed, off, dev)
         ctx.out_drop = (p_out, off_out)
@@ -770,7 +741,6 @@ class _LnFn(torch.autograd.Function):
         if dyb is not None:
             dyb = _rows(dyb, dy2.dtype)
         M = z.shape[0]
-        L = _lib.lib()
         dx = torch.empty_like(z)
         dres = torch.empty_like(z) if (ctx.has_res and p > 0) else None
         # gradient of the summand behind the norm: the (masked) dy — without output dropout it IS dy: handed on as such, no copy
@@ -788,17 +758,13 @@ class _LnFn(torch.autograd.Function):
         acc = int(sunk and not _first_touch(*ctx.gb))
         defer = acc == 1 and LnReduceQueue.enabled and M >= LnReduceQueue.MIN_ROWS
         if defer:       # arena slices (pre-zeroed, accumulating): leave the column partials behind, one reduction per backward pass
-            nparts = L.goat_ln_bwd_nparts(M)
+            nparts = _lib.lib().goat_ln_bwd_nparts(M)
             ws = torch.empty(nparts * 2 * H, dtype=torch.float32, device=z.device)
             acc = 2
         else:
-            ws = torch.empty(L.goat_ln_bwd_ws_floats(H), dtype=torch.float32, device=z.device) if (LN_DETERMINISTIC or M > LN_ATOMIC_MAX_ROWS) else None
-        st = L.goat_ln_bwd_do(_stream(), _dt(z), _ptr(dy2), _ptr(dyb) if dyb is not None else None, _ptr(z), _ptr(gamma), _ptr(mean), _ptr(rstd),
-                              p, seed, off, dev, _ptr(dx), _ptr(dres) if dres is not None else None,
-                              _ptr(dg), _ptr(db), _ptr(ws) if ws is not None else None, M, H,
-                              acc | (4 if (ctx.z_out and dskip is not None) else 0), _ptr(dskip) if dskip is not None else None,
-                              ctx.out_drop[0], ctx.out_drop[1], _ptr(dpost) if dpost is not None else None)
-        _lib.check(st, 'goat_ln_bwd')
+            ws = torch.empty(_lib.lib().goat_ln_bwd_ws_floats(H), dtype=torch.float32, device=z.device) if (LN_DETERMINISTIC or M > LN_ATOMIC_MAX_ROWS) else None
+        launch('goat_ln_bwd_do', _dt(z), dy2, dyb, z, gamma, mean, rstd, p, seed, off, dev, dx, dres, dg, db, ws, M, H,
+               acc | (4 if (ctx.z_out and dskip is not None) else 0), dskip, ctx.out_drop[0], ctx.out_drop[1], dpost)
         if defer:
             LnReduceQueue.push(ws, dg, db, nparts, H)
         if sunk:
@@ -828,14 +794,13 @@ FANOUT = os.environ.get('GOAT_NO_FANOUT', '0') != '1'        # (diagnostics: A/B
 
 def add_n(tensors, out=None):
     """out = sum(tensors) (same shape / dtype, contiguous), float32 accumulation, one launch (goat_add_n)."""
-    ts = [t if t.is_contiguous() else t.contiguous() for t in tensors]
+    ts = [t.contiguous() for t in tensors]
     out = torch.empty_like(ts[0]) if out is None else out
     while len(ts) > 8:                       # (never on the GOAT paths: at most 7 consumers)
         head = add_n(ts[:8])
         ts = [head] + ts[8:]
     arr = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    st = _lib.lib().goat_add_n(_stream(), _dt(ts[0]), arr, len(ts), _ptr(out), ts[0].numel())
-    _lib.check(st, 'goat_add_n')
+    launch('goat_add_n', _dt(ts[0]), arr, len(ts), out, ts[0].numel())
     return out
 
 
@@ -893,8 +858,7 @@ class _CeRowsFn(torch.autograd.Function):
         tg = targets.to(torch.int64).contiguous()
         loss = torch.empty(M, dtype=torch.float32, device=lg.device)
         lse = torch.empty(M, dtype=torch.float32, device=lg.device)
-        st = _lib.lib().goat_ce_fwd(_stream(), _ptr(lg), N, M, N, _ptr(tg), _ptr(loss), _ptr(lse))
-        _lib.check(st, 'goat_ce_fwd')
+        launch('goat_ce_fwd', lg, N, M, N, tg, loss, lse)
         ctx.save_for_backward(lg, tg, lse)
         ctx.in_dtype = logits.dtype
         return loss
@@ -904,8 +868,7 @@ class _CeRowsFn(torch.autograd.Function):
         lg, tg, lse = ctx.saved_tensors
         M, N = lg.shape
         dl = torch.empty_like(lg)
-        st = _lib.lib().goat_ce_bwd(_stream(), GOAT_F32, _ptr(lg), N, M, N, _ptr(tg), _ptr(lse), _ptr(dloss.float().contiguous()), _ptr(dl), N)
-        _lib.check(st, 'goat_ce_bwd')
+        launch('goat_ce_bwd', GOAT_F32, lg, N, M, N, tg, lse, dloss.float().contiguous(), dl, N)
         return (dl if ctx.in_dtype == torch.float32 else dl.to(ctx.in_dtype)), None
 
 
@@ -932,8 +895,7 @@ def zero_ranges(tensors):
             continue
         ptrs = (ctypes.c_void_p * len(grp))(*[t.data_ptr() for t in grp])
         nb = (ctypes.c_int64 * len(grp))(*[t.numel() * t.element_size() for t in grp])
-        st = _lib.lib().goat_zero_ranges(_stream(), ptrs, nb, len(grp))
-        _lib.check(st, 'goat_zero_ranges')
+        launch('goat_zero_ranges', ptrs, nb, len(grp))
 
 
 class _DropAddFn(torch.autograd.Function):
@@ -942,15 +904,13 @@ class _DropAddFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, p):
         _need_gpu(x)
-        xc = x if x.is_contiguous() else x.contiguous()
+        xc = x.contiguous()
         rc = None
         if residual is not None:
-            rc = residual if residual.is_contiguous() else residual.contiguous()
+            rc = residual.contiguous()
         y = torch.empty_like(xc)
         seed, off, dev = RngState.next(xc.numel()) if p > 0 else (0, 0, None)
-        st = _lib.lib().goat_dropout_add_fwd(_stream(), _dt(xc), _ptr(xc), _ptr(rc) if rc is not None else None,
-                                             _ptr(y), xc.numel(), p, seed, off, dev)
-        _lib.check(st, 'goat_dropout_add_fwd')
+        launch('goat_dropout_add_fwd', _dt(xc), xc, rc, y, xc.numel(), p, seed, off, dev)
         ctx.rng = (p, seed, off, dev)
         ctx.has_res = residual is not None
         return y
@@ -958,11 +918,10 @@ class _DropAddFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         p, seed, off, dev = ctx.rng
-        dyc = dy if dy.is_contiguous() else dy.contiguous()
+        dyc = dy.contiguous()
         if p > 0:
             dx = torch.empty_like(dyc)
-            st = _lib.lib().goat_dropout_bwd(_stream(), _dt(dyc), _ptr(dyc), _ptr(dx), dyc.numel(), p, seed, off, dev)
-            _lib.check(st, 'goat_dropout_bwd')
+            launch('goat_dropout_bwd', _dt(dyc), dyc, dx, dyc.numel(), p, seed, off, dev)
         else:
             dx = dyc
         return dx, (dyc if ctx.has_res else None), None
@@ -984,14 +943,23 @@ ATTN_MAXLK = 512            # goat_attn_long_fwd / goat_attn_long_bwd (key-strea
 
 
 def _attn_entry(Lk):
-    """The pair of library entry points serving Lk keys: the long pair only above the short pair's limit, so nothing changes below it."""
+    """Name stem of the pair of library entry points serving Lk keys (stem + '_fwd' / '_bwd'): the long pair only above the short
+    pair's limit, so nothing changes below it."""
     if Lk > ATTN_MAXLK:
         raise ValueError('attention over %d keys: the kernels serve at most %d (max_position_embeddings - 2 of the text encoder)'
                          % (Lk, ATTN_MAXLK))
-    h = _lib.lib()
-    if Lk > ATTN_SHORT_MAXLK:
-        return h.goat_attn_long_fwd, h.goat_attn_long_bwd, 'goat_attn_long'
-    return h.goat_attn_fwd, h.goat_attn_bwd, 'goat_attn'
+    return 'goat_attn_long' if Lk > ATTN_SHORT_MAXLK else 'goat_attn'
+
+
+def _attn_layout(a, b):
+    """(pointer, row stride, batch stride) of q, k and v, nine C arguments in a row, and the sizes (B, Lq, Lk, H): of the packed
+    projections as _AttnFn takes them, or of gradient buffers laid out like them (b: rows at its own leading dimension)."""
+    B, Lq, W = a.shape
+    if b is None:
+        H = W // 3
+        return (_ptr(a), W, Lq * W, _ptr(a, H), W, Lq * W, _ptr(a, 2 * H), W, Lq * W), (B, Lq, Lq, H)
+    Lk, ld = b.shape[1], b.stride(1)
+    return (_ptr(a), W, Lq * W, _ptr(b), ld, Lk * ld, _ptr(b, W), ld, Lk * ld), (B, Lq, Lk, W)
 
 
 class _AttnFn(torch.autograd.Function):
@@ -1003,7 +971,7 @@ class _AttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b, kmask, bias, nh, p):
         _need_gpu(a)
-        a = a if a.is_contiguous() else a.contiguous()
+        a = a.contiguous()
         slot = None
         if b is not None:
             # a view of a projection bank (linear_bank): rows at the bank's leading dimension; its gradient goes into the bank's buffer
@@ -1014,22 +982,9 @@ class _AttnFn(torch.autograd.Function):
             else:
                 b = b.contiguous()
         ctx.slot = slot
-        if b is None:
-            B, Lq, H3 = a.shape
-            H = H3 // 3
-            Lk = Lq
-            q = (a, 0, H3, Lq * H3)
-            k = (a, H, H3, Lq * H3)
-            v = (a, 2 * H, H3, Lq * H3)
-        else:
-            B, Lq, H = a.shape
-            Lk = b.shape[1]
-            ldb = b.stride(1)
-            q = (a, 0, H, Lq * H)
-            k = (b, 0, ldb, Lk * ldb)
-            v = (b, H, ldb, Lk * ldb)
+        qkv, (B, Lq, Lk, H) = _attn_layout(a, b)
         assert H == nh * 64, 'head_dim must be 64'
-        fwd, _, name = _attn_entry(Lk)
+        name = _attn_entry(Lk)
         o = torch.empty((B, Lq, H), dtype=a.dtype, device=a.device)
         lse = torch.empty((B, nh, Lq), dtype=torch.float32, device=a.device)
         if kmask is not None:
@@ -1038,13 +993,8 @@ class _AttnFn(torch.autograd.Function):
             bias = bias.contiguous().float()
         seed, off, dev = RngState.next(B * nh * Lq * Lk) if p > 0 else (0, 0, None)
         scale = 1.0 / math.sqrt(64.0)
-        st = fwd(
-            _stream(), _dt(a),
-            _ptr(q[0], q[1]), q[2], q[3], _ptr(k[0], k[1]), k[2], k[3], _ptr(v[0], v[1]), v[2], v[3],
-            _ptr(o), H, Lq * H,
-            _ptr(kmask) if kmask is not None else None, _ptr(bias) if bias is not None else None, _ptr(lse),
-            B, nh, Lq, Lk, scale, p, seed, off, dev)
-        _lib.check(st, '%s_fwd(Lq=%d,Lk=%d)' % (name, Lq, Lk))
+        launch(name + '_fwd', _dt(a), *qkv, o, H, Lq * H, kmask, bias, lse, B, nh, Lq, Lk, scale, p, seed, off, dev,
+               what='%s_fwd(Lq=%d,Lk=%d)' % (name, Lq, Lk))
         ctx.save_for_backward(a, b, kmask, bias, o, lse)
         ctx.cfg = (nh, p, seed, off, dev, scale)
         return o
@@ -1053,36 +1003,19 @@ class _AttnFn(torch.autograd.Function):
     def backward(ctx, do):
         a, b, kmask, bias, o, lse = ctx.saved_tensors
         nh, p, seed, off, dev, scale = ctx.cfg
-        do = do if do.is_contiguous() else do.contiguous()
+        do = do.contiguous()
         da = torch.empty_like(a)
         db = None
         if b is not None:
             db = ctx.slot[0].view(ctx.slot[1]) if ctx.slot is not None else torch.empty(b.shape, dtype=b.dtype, device=b.device)
-        if b is None:
-            B, Lq, H3 = a.shape
-            H = H3 // 3
-            Lk = Lq
-            q, k, v = (a, 0, H3, Lq * H3), (a, H, H3, Lq * H3), (a, 2 * H, H3, Lq * H3)
-            dq, dk, dv = (da, 0, H3, Lq * H3), (da, H, H3, Lq * H3), (da, 2 * H, H3, Lq * H3)
-        else:
-            B, Lq, H = a.shape
-            Lk = b.shape[1]
-            ldb, ldg = b.stride(1), db.stride(1)
-            q, k, v = (a, 0, H, Lq * H), (b, 0, ldb, Lk * ldb), (b, H, ldb, Lk * ldb)
-            dq, dk, dv = (da, 0, H, Lq * H), (db, 0, ldg, Lk * ldg), (db, H, ldg, Lk * ldg)
+        qkv, (B, Lq, Lk, H) = _attn_layout(a, b)
+        dqkv, _ = _attn_layout(da, db)
         dbias = None
         if bias is not None and ctx.needs_input_grad[3]:
             dbias = torch.zeros_like(bias)
-        _, bwd, name = _attn_entry(Lk)
-        st = bwd(
-            _stream(), _dt(a),
-            _ptr(q[0], q[1]), q[2], q[3], _ptr(k[0], k[1]), k[2], k[3], _ptr(v[0], v[1]), v[2], v[3],
-            _ptr(o), H, Lq * H, _ptr(do), H, Lq * H,
-            _ptr(dq[0], dq[1]), dq[2], dq[3], _ptr(dk[0], dk[1]), dk[2], dk[3], _ptr(dv[0], dv[1]), dv[2], dv[3],
-            _ptr(kmask) if kmask is not None else None, _ptr(bias) if bias is not None else None, _ptr(lse),
-            _ptr(dbias) if dbias is not None else None,
-            B, nh, Lq, Lk, scale, p, seed, off, dev)
-        _lib.check(st, '%s_bwd(Lq=%d,Lk=%d)' % (name, Lq, Lk))
+        name = _attn_entry(Lk)
+        launch(name + '_bwd', _dt(a), *qkv, o, H, Lq * H, do, H, Lq * H, *dqkv, kmask, bias, lse, dbias, B, nh, Lq, Lk, scale, p, seed, off, dev,
+               what='%s_bwd(Lq=%d,Lk=%d)' % (name, Lq, Lk))
         return da, db, None, dbias, None, None
 
 
@@ -1153,15 +1086,13 @@ def attn_decode(q, kv_new, cache, kmask, pos, nh, p=0.0):
     for name, t in (('q', q), ('kv_new', kv_new), ('kmask', kmask), ('pos', pos)):
         if t is not None and t.device != cache.device:
             raise ValueError('attn_decode: %s is on %s, the cache on %s' % (name, t.device, cache.device))
-    qc = q if q.is_contiguous() else q.contiguous()
-    kvc = kv_new if kv_new.is_contiguous() else kv_new.contiguous()
+    qc = q.contiguous()
+    kvc = kv_new.contiguous()
     o = torch.empty_like(qc)
     p = float(p)
     seed, off, dev = RngState.next(B * nh * Lmax) if p > 0 else (0, 0, None)
-    st = _lib.lib().goat_attn_decode_fwd(_stream(), _dt(qc), _ptr(qc), _ptr(kvc), _ptr(cache), cache.stride(1), cache.stride(0), _ptr(o),
-                                         _ptr(kmask) if kmask is not None else None, _ptr(pos), B, int(nh), Lmax,
-                                         1.0 / math.sqrt(64.0), p, seed, off, dev)
-    _lib.check(st, 'goat_attn_decode_fwd(B=%d,nh=%d,Lmax=%d)' % (B, nh, Lmax))
+    launch('goat_attn_decode_fwd', _dt(qc), qc, kvc, cache, cache.stride(1), cache.stride(0), o, kmask, pos, B, int(nh), Lmax, 1.0 / math.sqrt(64.0),
+           p, seed, off, dev, what='goat_attn_decode_fwd(B=%d,nh=%d,Lmax=%d)' % (B, nh, Lmax))
     return o
 
 
@@ -1186,10 +1117,8 @@ def decode_select(logits, state, unk, eos, pad, sampling=False, n_valid=None):
         if t.device != logits.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
             raise ValueError('decode_select: state.%s must be a contiguous %s %s on %s' % (name, dtype, list(shape), logits.device))
     seed, off, dev = RngState.next(B * V) if sampling else (0, 0, None)
-    st = _lib.lib().goat_decode_select(_stream(), _ptr(logits), logits.stride(0), B, V, state.Lmax, int(unk), int(eos), int(pad),
-                                       1 if sampling else 0, seed, off, dev, _ptr(state.pos), _ptr(state.words), _ptr(state.kmask),
-                                       _ptr(state.ended), _ptr(state.end_step), _ptr(state.n_live))
-    _lib.check(st, 'goat_decode_select(B=%d,V=%d)' % (B, V))
+    launch('goat_decode_select', logits, logits.stride(0), B, V, state.Lmax, int(unk), int(eos), int(pad), 1 if sampling else 0, seed, off, dev,
+           state.pos, state.words, state.kmask, state.ended, state.end_step, state.n_live, what='goat_decode_select(B=%d,V=%d)' % (B, V))
 
 
 # ----------------------------------------------------------------------------- pano fusion / gather
@@ -1199,14 +1128,12 @@ class _PanoFusionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, a_w, a_b):
         _need_gpu(x)
-        x = x if x.is_contiguous() else x.contiguous()
+        x = x.contiguous()
         N, V, H = x.shape
         fused = torch.empty((N, H), dtype=x.dtype, device=x.device)
         wsave = torch.empty((N, V), dtype=torch.float32, device=x.device)
         av = a_w.detach().reshape(-1).contiguous()
-        st = _lib.lib().goat_pano_fusion_fwd(_stream(), _dt(x), _ptr(x), _ptr(av), _ptr(a_b), _ptr(fused),
-                                             _ptr(wsave), N, V, H)
-        _lib.check(st, 'goat_pano_fusion_fwd')
+        launch('goat_pano_fusion_fwd', _dt(x), x, av, a_b, fused, wsave, N, V, H)
         ctx.save_for_backward(x, av, a_b, wsave)
         ctx.wshape = a_w.shape
         ctx.params = (a_w, a_b)
@@ -1216,7 +1143,7 @@ class _PanoFusionFn(torch.autograd.Function):
     def backward(ctx, df):
         x, av, a_b, wsave = ctx.saved_tensors
         N, V, H = x.shape
-        df = df if df.is_contiguous() else df.contiguous()
+        df = df.contiguous()
         dx = torch.empty_like(x)
         sinks = small_sinks(ctx.params)      # (bound slices are cleared on first touch whether the kernel then adds into them or not)
         sunk = PANO_SINK and sinks is not None and sinks[0].is_contiguous()
@@ -1225,9 +1152,7 @@ class _PanoFusionFn(torch.autograd.Function):
         else:
             da = torch.zeros(H, dtype=torch.float32, device=x.device)
             da0 = torch.zeros(1, dtype=torch.float32, device=x.device)
-        st = _lib.lib().goat_pano_fusion_bwd(_stream(), _dt(x), _ptr(x), _ptr(av), _ptr(a_b), _ptr(wsave), _ptr(df),
-                                             _ptr(dx), _ptr(da), _ptr(da0), N, V, H)
-        _lib.check(st, 'goat_pano_fusion_bwd')
+        launch('goat_pano_fusion_bwd', _dt(x), x, av, a_b, wsave, df, dx, da, da0, N, V, H)
         if sunk:
             return dx, None, None
         return dx, da.view(ctx.wshape), da0
@@ -1243,13 +1168,11 @@ class _GatherFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src, idx, start, scale, n_out, inverse):
         _need_gpu(src)
-        src = src if src.is_contiguous() else src.contiguous()
+        src = src.contiguous()
         H = src.shape[-1]
         s2 = src.reshape(-1, H)
         out = torch.empty((n_out, H), dtype=src.dtype, device=src.device)
-        st = _lib.lib().goat_gather_segmean_fwd(_stream(), _dt(s2), _ptr(s2), s2.shape[0], _ptr(idx), _ptr(start),
-                                                _ptr(scale) if scale is not None else None, _ptr(out), n_out, H, None)
-        _lib.check(st, 'goat_gather_segmean_fwd')
+        launch('goat_gather_segmean_fwd', _dt(s2), s2, s2.shape[0], idx, start, scale, out, n_out, H, None)
         ctx.save_for_backward(idx, start, scale)
         ctx.sshape, ctx.sdtype = src.shape, src.dtype
         ctx.inverse = inverse
@@ -1258,7 +1181,7 @@ class _GatherFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         idx, start, scale = ctx.saved_tensors
-        dout = dout if dout.is_contiguous() else dout.contiguous()
+        dout = dout.contiguous()
         n_out, H = dout.shape
         rows = 1
         for s in ctx.sshape[:-1]:
@@ -1270,14 +1193,11 @@ class _GatherFn(torch.autograd.Function):
                 raise ValueError('inverse gather index covers %d rows, the source has %d' % (inv_start.numel() - 1, rows))
             d2 = dout if dout.dtype == ctx.sdtype else dout.to(ctx.sdtype)
             dsrc = torch.empty((rows, H), dtype=ctx.sdtype, device=dout.device)
-            st = _lib.lib().goat_gather_segmean_fwd(_stream(), _dt(d2), _ptr(d2), n_out, _ptr(inv_idx), _ptr(inv_start), None, _ptr(dsrc),
-                                                    rows, H, _ptr(inv_w) if inv_w is not None else None)
-            _lib.check(st, 'goat_gather_segmean_fwd (inverse)')
+            launch('goat_gather_segmean_fwd', _dt(d2), d2, n_out, inv_idx, inv_start, None, dsrc, rows, H, inv_w,
+                   what='goat_gather_segmean_fwd (inverse)')
             return dsrc.view(ctx.sshape), None, None, None, None, None
         d32 = torch.zeros((rows, H), dtype=torch.float32, device=dout.device)
-        st = _lib.lib().goat_gather_segmean_bwd(_stream(), _dt(dout), _ptr(dout), _ptr(idx), _ptr(start),
-                                                _ptr(scale) if scale is not None else None, _ptr(d32), n_out, H)
-        _lib.check(st, 'goat_gather_segmean_bwd')
+        launch('goat_gather_segmean_bwd', _dt(dout), dout, idx, start, scale, d32, n_out, H)
         return d32.to(ctx.sdtype).view(ctx.sshape), None, None, None, None, None
 
 
@@ -1325,7 +1245,7 @@ class _EmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ids, word, type_tab, type_ids, pos_tab, out_dtype, word_pad, pos_pad):
         _need_gpu(word)
-        ids = ids if ids.is_contiguous() else ids.contiguous()
+        ids = ids.contiguous()
         if ids.dtype != torch.int64:
             ids = ids.long()
         if type_ids is not None:
@@ -1336,11 +1256,7 @@ class _EmbedFn(torch.autograd.Function):
         if pos_tab is not None and L > pos_tab.shape[0]:
             raise IndexError('sequence length %d exceeds the position table (%d rows)' % (L, pos_tab.shape[0]))
         out = torch.empty(tuple(ids.shape) + (H,), dtype=out_dtype, device=word.device)
-        st = _lib.lib().goat_embed_fwd(_stream(), _dt(out), _ptr(word), _ptr(ids), _ptr(type_tab) if type_tab is not None else None,
-                                       _ptr(type_ids) if type_ids is not None else None,
-                                       _ptr(pos_tab) if pos_tab is not None else None, L, _ptr(out), rows, H, V,
-                                       _ptr(_embed_err(word.device)))
-        _lib.check(st, 'goat_embed_fwd')
+        launch('goat_embed_fwd', _dt(out), word, ids, type_tab, type_ids, pos_tab, L, out, rows, H, V, _embed_err(word.device))
         ctx.tabs = (word, type_tab, pos_tab)
         ctx.save_for_backward(ids, type_ids)
         ctx.meta = (V, H, L, None if type_tab is None else type_tab.shape[0], None if pos_tab is None else pos_tab.shape[0],
@@ -1351,7 +1267,7 @@ class _EmbedFn(torch.autograd.Function):
     def backward(ctx, dout):
         ids, type_ids = ctx.saved_tensors
         V, H, L, TV, P, word_pad, pos_pad = ctx.meta
-        dout = dout if dout.is_contiguous() else dout.contiguous()
+        dout = dout.contiguous()
         d2 = dout.view(-1, H)
         rows = d2.shape[0]
         need_w, need_t, need_p = ctx.needs_input_grad[1], TV is not None and ctx.needs_input_grad[2], \
@@ -1368,11 +1284,7 @@ class _EmbedFn(torch.autograd.Function):
         dtab = (st_ if st_ is not None else torch.zeros((TV, H), dtype=torch.float32, device=dev)) if need_t else None
         dpos = (sp if sp is not None else torch.zeros((P, H), dtype=torch.float32, device=dev)) if need_p else None
         if need_w or (need_t and type_ids is not None):
-            st = _lib.lib().goat_embed_bwd(_stream(), _dt(d2), _ptr(d2), _ptr(ids), _ptr(type_ids) if type_ids is not None else None,
-                                           L, _ptr(dword) if need_w else None,
-                                           _ptr(dtab) if (need_t and type_ids is not None) else None,
-                                           None, rows, H, V, word_pad, pos_pad)
-            _lib.check(st, 'goat_embed_bwd')
+            launch('goat_embed_bwd', _dt(d2), d2, ids, type_ids, L, dword, dtab if type_ids is not None else None, None, rows, H, V, word_pad, pos_pad)
         if need_p:
             # position ids are arange(L) for every sample: d pos[:L] = column sums of dout viewed as [rows/L, L*H]
             # (the padding row, if any, is skipped: nn.Embedding(padding_idx) gives it no gradient)
@@ -1392,11 +1304,10 @@ class _EmbedFn(torch.autograd.Function):
 
 def embedding_scatter_add(dword, rows, ids, word_pad=-1):
     """dword[ids[r], :] += rows[r, :] (float32 table gradient, atomics) — goat_embed_bwd on the word table only."""
-    rows = rows if rows.is_contiguous() else rows.contiguous()
+    rows = rows.contiguous()
     ids = ids.reshape(-1).contiguous()
-    st = _lib.lib().goat_embed_bwd(_stream(), _dt(rows), _ptr(rows), _ptr(ids), None, 1, _ptr(dword), None, None,
-                                   rows.shape[0], rows.shape[1], dword.shape[0], -1 if word_pad is None else int(word_pad), -1)
-    _lib.check(st, 'goat_embed_bwd')
+    launch('goat_embed_bwd', _dt(rows), rows, ids, None, 1, dword, None, None, rows.shape[0], rows.shape[1], dword.shape[0],
+           -1 if word_pad is None else int(word_pad), -1)
 
 
 def embedding(ids, word, type_tab=None, type_ids=None, pos_tab=None, out_dtype=None, word_pad=None, pos_pad=None):
@@ -1410,7 +1321,7 @@ class _AttnPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, smask=None):
         _need_gpu(x)
-        x = x if x.is_contiguous() else x.contiguous()
+        x = x.contiguous()
         B, L, H = x.shape
         wv = w.detach().reshape(-1).float().contiguous()
         out = torch.empty((B, H), dtype=torch.float32, device=x.device)
@@ -1418,9 +1329,7 @@ class _AttnPoolFn(torch.autograd.Function):
         ws = torch.empty(B * L, dtype=torch.float32, device=x.device)
         if smask is not None:
             assert smask.shape == (B, L) and smask.dtype == torch.float32 and smask.is_contiguous()
-        st = _lib.lib().goat_attn_pool_fwd(_stream(), _dt(x), _ptr(x), _ptr(wv), _ptr(out), _ptr(attn), _ptr(ws), B, L, H,
-                                           _ptr(smask) if smask is not None else None)
-        _lib.check(st, 'goat_attn_pool_fwd')
+        launch('goat_attn_pool_fwd', _dt(x), x, wv, out, attn, ws, B, L, H, smask)
         ctx.save_for_backward(x, wv, attn, out)
         ctx.wshape = w.shape
         return out
@@ -1433,9 +1342,7 @@ class _AttnPoolFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dw = torch.zeros(H, dtype=torch.float32, device=x.device)
         ws = torch.empty(B * L, dtype=torch.float32, device=x.device)
-        st = _lib.lib().goat_attn_pool_bwd(_stream(), _dt(x), _ptr(x), _ptr(wv), _ptr(attn), _ptr(out), _ptr(dout), _ptr(dx),
-                                           _ptr(dw), _ptr(ws), B, L, H)
-        _lib.check(st, 'goat_attn_pool_bwd')
+        launch('goat_attn_pool_bwd', _dt(x), x, wv, attn, out, dout, dx, dw, ws, B, L, H)
         return dx, dw.view(ctx.wshape), None
 
 
@@ -1458,9 +1365,7 @@ class _DoorGateFn(torch.autograd.Function):
         rows = a2.shape[0]
         out = torch.empty_like(a2)
         gate = torch.empty(rows, dtype=torch.float32, device=a2.device)
-        st = _lib.lib().goat_door_gate_fwd(_stream(), _dt(a2), _ptr(a2), _ptr(o2), _ptr(wav), _ptr(wov), _ptr(ba.detach()),
-                                           _ptr(bo.detach()), _ptr(out), _ptr(gate), rows, H)
-        _lib.check(st, 'goat_door_gate_fwd')
+        launch('goat_door_gate_fwd', _dt(a2), a2, o2, wav, wov, ba.detach(), bo.detach(), out, gate, rows, H)
         ctx.save_for_backward(a2, o2, wav, wov, gate)
         ctx.shapes = (aug.shape, ori.shape, ori.dtype, wa.shape, wo.shape)
         ctx.params = (wa, ba, wo, bo)
@@ -1478,14 +1383,10 @@ class _DoorGateFn(torch.autograd.Function):
             # gradient arena: the four gate parameters are small (cleared by GradArena.zero at the start of the step, never a first touch) —
             # the kernel's atomics add straight into their slices; a gate used in every step of an episode would otherwise cost a zero fill,
             # a clone and four AccumulateGrad adds per use
-            st = _lib.lib().goat_door_gate_bwd(_stream(), _dt(a2), _ptr(a2), _ptr(o2), _ptr(wav), _ptr(wov), _ptr(gate), _ptr(d2),
-                                               _ptr(daug), _ptr(dori), _ptr(sinks[0]), _ptr(sinks[2]), _ptr(sinks[1]), rows, H, _ptr(sinks[3]))
-            _lib.check(st, 'goat_door_gate_bwd')
+            launch('goat_door_gate_bwd', _dt(a2), a2, o2, wav, wov, gate, d2, daug, dori, sinks[0], sinks[2], sinks[1], rows, H, sinks[3])
             return daug.view(ashape), dori.view(oshape).to(odtype), None, None, None, None
         buf = torch.zeros(2 * H + 1, dtype=torch.float32, device=a2.device)
-        st = _lib.lib().goat_door_gate_bwd(_stream(), _dt(a2), _ptr(a2), _ptr(o2), _ptr(wav), _ptr(wov), _ptr(gate), _ptr(d2),
-                                           _ptr(daug), _ptr(dori), _ptr(buf), _ptr(buf, H), _ptr(buf, 2 * H), rows, H, None)
-        _lib.check(st, 'goat_door_gate_bwd')
+        launch('goat_door_gate_bwd', _dt(a2), a2, o2, wav, wov, gate, d2, daug, dori, buf, _ptr(buf, H), _ptr(buf, 2 * H), rows, H, None)
         db = buf[2 * H:]          # both biases receive the same gradient (distinct tensors: autograd may keep them as .grad)
         return daug.view(ashape), dori.view(oshape).to(odtype), buf[:H].view(washape), db, buf[H:2 * H].view(woshape), db.clone()
 
@@ -1505,8 +1406,7 @@ class _DictWsumFn(torch.autograd.Function):
         pf = p.float().reshape(p.shape[0], p.shape[1]).contiguous()
         B, K, H = zf.shape
         out = torch.empty((B, 1, H), dtype=out_dtype, device=z.device)
-        st = _lib.lib().goat_dict_wsum_fwd(_stream(), _dt(out), _ptr(zf), _ptr(pf), _ptr(out), B, K, H)
-        _lib.check(st, 'goat_dict_wsum_fwd')
+        launch('goat_dict_wsum_fwd', _dt(out), zf, pf, out, B, K, H)
         ctx.save_for_backward(zf, pf)
         ctx.meta = (z.dtype, p.shape, p.dtype)
         return out
@@ -1519,9 +1419,7 @@ class _DictWsumFn(torch.autograd.Function):
         d2 = _rows(dout)
         dz = torch.empty_like(zf) if ctx.needs_input_grad[0] else None
         dp = torch.empty_like(pf) if ctx.needs_input_grad[1] else None
-        st = _lib.lib().goat_dict_wsum_bwd(_stream(), _dt(d2), _ptr(d2), _ptr(zf), _ptr(pf), _ptr(dz) if dz is not None else None,
-                                           _ptr(dp) if dp is not None else None, B, K, H)
-        _lib.check(st, 'goat_dict_wsum_bwd')
+        launch('goat_dict_wsum_bwd', _dt(d2), d2, zf, pf, dz, dp, B, K, H)
         return (dz.to(zdtype) if dz is not None else None, dp.view(pshape).to(pdtype) if dp is not None else None, None)
 
 
@@ -1538,7 +1436,7 @@ def _u8(t):
     """bool / uint8 mask -> contiguous byte tensor (a view for bool: same storage)."""
     if t is None:
         return None
-    t = t if t.is_contiguous() else t.contiguous()
+    t = t.contiguous()
     return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
@@ -1569,12 +1467,9 @@ class _SapFuseFn(torch.autograd.Function):
         labels = ga is not None
         loss = torch.empty(B, dtype=torch.float32, device=dev) if labels else None
         lse = torch.empty((B, 3), dtype=torch.float32, device=dev) if labels else None
-        P = lambda t: _ptr(t) if t is not None else None
         ctx.cfg = (_dt(gs), int(bool(fw_sigmoid)), int(bool(lmask_is_valid)), int(bool(add_stop)), B, G, W)
-        st = _lib.lib().goat_sap_fuse_fwd(_stream(), ctx.cfg[0], _ptr(gs), _ptr(ls), P(fwl), ctx.cfg[1], P(gvis), P(gvalid), P(glens),
-                                          P(lmask), ctx.cfg[2], P(M), ctx.cfg[3], P(ga), P(la), _ptr(gl), _ptr(ll), _ptr(fused),
-                                          P(loss), P(lse), B, G, W)
-        _lib.check(st, 'goat_sap_fuse_fwd')
+        launch('goat_sap_fuse_fwd', ctx.cfg[0], gs, ls, fwl, ctx.cfg[1], gvis, gvalid, glens, lmask, ctx.cfg[2], M, ctx.cfg[3], ga, la, gl, ll, fused,
+               loss, lse, B, G, W)
         ctx.opt = (fwl, gvis, gvalid, glens, lmask, M, ga, la, lse)
         ctx.save_for_backward(gs, ls, gl, ll, fused)
         return gl, ll, fused, loss
@@ -1588,11 +1483,8 @@ class _SapFuseFn(torch.autograd.Function):
         dgl, dll, dfused, dloss = f(dgl), f(dll), f(dfused), f(dloss)
         dgs, dls = torch.empty_like(gs), torch.empty_like(ls)
         dfw = torch.empty_like(fwl) if fwl is not None else None
-        P = lambda t: _ptr(t) if t is not None else None
-        st = _lib.lib().goat_sap_fuse_bwd(_stream(), dtc, _ptr(gs), _ptr(ls), P(fwl), fw_sig, P(gvis), P(gvalid), P(glens), P(lmask), lvalid,
-                                          P(M), add_stop, P(ga), P(la), _ptr(gl), _ptr(ll), _ptr(fused), P(lse), P(dloss), P(dgl), P(dll),
-                                          P(dfused), _ptr(dgs), _ptr(dls), P(dfw), B, G, W)
-        _lib.check(st, 'goat_sap_fuse_bwd')
+        launch('goat_sap_fuse_bwd', dtc, gs, ls, fwl, fw_sig, gvis, gvalid, glens, lmask, lvalid, M, add_stop, ga, la, gl, ll, fused, lse, dloss, dgl,
+               dll, dfused, dgs, dls, dfw, B, G, W)
         return dgs, dls, (None if dfw is None else dfw.view(ctx.fw_shape)), None, None, None, None, None, None, None, None, None, None
 
 
@@ -1621,9 +1513,7 @@ class _InfoNceFn(torch.autograd.Function):
         prob = torch.empty((6, Bl, Ba), dtype=torch.float32, device=ins[0].device)
         xl = (ctypes.c_void_p * 3)(*[_ptr(t) for t in ins[0:3]])
         xa = (ctypes.c_void_p * 3)(*[_ptr(t) for t in ins[4:7]])
-        st = _lib.lib().goat_infonce_fwd(_stream(), xl, xa, _ptr(ins[3]), _ptr(ins[7]), _ptr(loss), _ptr(prob), Bl, Ba, H,
-                                         int(target0), float(temperature))
-        _lib.check(st, 'goat_infonce_fwd')
+        launch('goat_infonce_fwd', xl, xa, ins[3], ins[7], loss, prob, Bl, Ba, H, int(target0), float(temperature))
         ctx.save_for_backward(prob, *ins)
         ctx.same = tuple(a is b for a, b in zip((g_loc, v_loc, f_loc, t_loc), (g_all, v_all, f_all, t_all)))
         ctx.cfg = (Bl, Ba, H, int(target0), float(temperature))
@@ -1643,9 +1533,7 @@ class _InfoNceFn(torch.autograd.Function):
         xa = (ctypes.c_void_p * 3)(*[_ptr(t) for t in ins[4:7]])
         dxl = (ctypes.c_void_p * 3)(*[_ptr(t) for t in gl[0:3]])
         dxa = (ctypes.c_void_p * 3)(*[_ptr(t) for t in ga[0:3]])
-        st = _lib.lib().goat_infonce_bwd(_stream(), xl, xa, _ptr(ins[3]), _ptr(ins[7]), _ptr(dloss.float().contiguous()), _ptr(prob),
-                                         dxl, dxa, _ptr(gl[3]), _ptr(ga[3]), Bl, Ba, H, target0, temperature)
-        _lib.check(st, 'goat_infonce_bwd')
+        launch('goat_infonce_bwd', xl, xa, ins[3], ins[7], dloss.float().contiguous(), prob, dxl, dxa, gl[3], ga[3], Bl, Ba, H, target0, temperature)
         return tuple(gl) + tuple((ga[k] if need_all[k] else None) for k in range(4)) + (None, None)
 
 
@@ -1653,17 +1541,14 @@ def _cfp_mix_fwd(go, vo, fwl):
     B, H = go.shape
     fo = torch.empty_like(go)
     fw = torch.empty(B, dtype=torch.float32, device=go.device)
-    st = _lib.lib().goat_cfp_mix_fwd(_stream(), _dt(fwl), _ptr(go), _ptr(vo), _ptr(fwl), _ptr(fo), _ptr(fw), B, H)
-    _lib.check(st, 'goat_cfp_mix_fwd')
+    launch('goat_cfp_mix_fwd', _dt(fwl), go, vo, fwl, fo, fw, B, H)
     return fo, fw
 
 
 def _cfp_mix_bwd(go, vo, fw, dfo, dgo, dvo, fwl_dtype, accumulate):
     B, H = go.shape
     dfwl = torch.empty(B, dtype=fwl_dtype, device=go.device)
-    st = _lib.lib().goat_cfp_mix_bwd(_stream(), GOAT_BF16 if fwl_dtype == torch.bfloat16 else GOAT_F32, _ptr(go), _ptr(vo), _ptr(fw), _ptr(dfo),
-                                     _ptr(dgo), _ptr(dvo), _ptr(dfwl), B, H, int(accumulate))
-    _lib.check(st, 'goat_cfp_mix_bwd')
+    launch('goat_cfp_mix_bwd', GOAT_BF16 if fwl_dtype == torch.bfloat16 else GOAT_F32, go, vo, fw, dfo, dgo, dvo, dfwl, B, H, int(accumulate))
     return dfwl
 
 
@@ -1723,8 +1608,7 @@ class _CfpTailFn(torch.autograd.Function):
         loss = torch.zeros(Bl, dtype=torch.float32, device=go.device)
         prob = torch.empty((6, Bl, Bl), dtype=torch.float32, device=go.device)
         xs = (ctypes.c_void_p * 3)(_ptr(go), _ptr(vo), _ptr(fo))
-        st = _lib.lib().goat_infonce_fwd(_stream(), xs, xs, _ptr(to), _ptr(to), _ptr(loss), _ptr(prob), Bl, Bl, H, 0, float(temperature))
-        _lib.check(st, 'goat_infonce_fwd')
+        launch('goat_infonce_fwd', xs, xs, to, to, loss, prob, Bl, Bl, H, 0, float(temperature))
         ctx.save_for_backward(go, vo, fo, to, fw, prob)
         ctx.fshape, ctx.fdtype, ctx.temperature = fwl.shape, f1.dtype, float(temperature)
         return loss
@@ -1736,9 +1620,7 @@ class _CfpTailFn(torch.autograd.Function):
         d = torch.zeros((4, Bl, H), dtype=torch.float32, device=go.device)          # dgo | dvo | dfo | dto, accumulated by the kernels
         xs = (ctypes.c_void_p * 3)(_ptr(go), _ptr(vo), _ptr(fo))
         dx = (ctypes.c_void_p * 3)(_ptr(d[0]), _ptr(d[1]), _ptr(d[2]))
-        st = _lib.lib().goat_infonce_bwd(_stream(), xs, xs, _ptr(to), _ptr(to), _ptr(dloss.float().contiguous()), _ptr(prob), dx, dx, _ptr(d[3]), _ptr(d[3]),
-                                         Bl, Bl, H, 0, ctx.temperature)
-        _lib.check(st, 'goat_infonce_bwd')
+        launch('goat_infonce_bwd', xs, xs, to, to, dloss.float().contiguous(), prob, dx, dx, d[3], d[3], Bl, Bl, H, 0, ctx.temperature)
         dfwl = _cfp_mix_bwd(go, vo, fw, d[2], d[0], d[1], ctx.fdtype, True)
         return d[0], d[1], dfwl.view(ctx.fshape), d[3], None
 

@@ -16,6 +16,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._plumbing import launch
 from .shadows import BPAD, CAT, CATB, PLAIN, ROWPAD, key_kind, member_ids
 
 NO_DECAY = ('bias', 'LayerNorm.bias', 'LayerNorm.weight')      # P/optim/misc.py:13
@@ -152,8 +153,7 @@ class FusedAdamW:
         pl = self._plan(task)
         if not pl['params']:
             return
-        arena, lib = self.arena, _lib.lib()
-        st = torch.cuda.current_stream().cuda_stream
+        arena = self.arena
         b1, b2 = self.betas
         slots, done = self._copies(pl['params'])
         host = pl['host']
@@ -189,10 +189,9 @@ class FusedAdamW:
             pl['dev'].copy_(raw)
         self._sq.zero_()
         clip = max_norm is not None and max_norm > 0
-        _lib.check(lib.goat_grad_sqnorm(st, arena.flat.data_ptr(), pl['ranges'].data_ptr(), pl['n_ranges'], self._sq.data_ptr()), 'goat_grad_sqnorm')
-        _lib.check(lib.goat_adamw_step(st, arena.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), pl['dev'].data_ptr(),
-                                       pl['chunks'].data_ptr(), pl['nchunks'], b1, b2, self.eps, float(max_norm) if clip else 0.0,
-                                       self._sq.data_ptr()), 'goat_adamw_step')
+        launch('goat_grad_sqnorm', arena.flat, pl['ranges'], pl['n_ranges'], self._sq)
+        launch('goat_adamw_step', arena.flat, self.exp_avg, self.exp_avg_sq, pl['dev'], pl['chunks'], pl['nchunks'], b1, b2, self.eps,
+               float(max_norm) if clip else 0.0, self._sq)
         # the copies the kernel did not cover (transposed / float32 images of the parity mode, a third bf16 copy): same storage, new values
         by_id = self._by_id
         self.last_refreshed = sum(hipops.refresh_shadows(p, by_id, done) for p in pl['params'])

@@ -10,9 +10,8 @@ import os
 
 import torch
 
-from . import _lib
 from ._lib import EPI_NONE
-from ._plumbing import _dt, _ptr, _stream
+from ._plumbing import _dt, call, cargs
 
 PROFILE = None   # bench.py sets this to a list to time every GEMM launch with HIP events (hipops.gemm / gemm_nt, WgradQueue._launch)
 
@@ -134,14 +133,11 @@ def _heuristic_cfg(ta, tb, M, N, Kc, split_k):
 
 
 def _launch_gemm_bf16(a, b, out, ta, tb, M, N, Kc, bias, epi, aux, split_k, bm, nstage, colsum_out):
-    args = (_stream(), int(ta), int(tb), _dt(out), _ptr(a), a.stride(0), _ptr(b), b.stride(0),
-            _ptr(out), out.stride(0), M, N, Kc,
-            _ptr(bias) if bias is not None else None, epi,
-            _ptr(aux) if aux is not None else None,
-            aux.stride(0) if aux is not None else 0, split_k, bm, nstage,
-            _ptr(colsum_out) if colsum_out is not None else None)
-    st = _lib.lib().goat_gemm_bf16(*args)
-    _lib.check(st, 'goat_gemm_bf16(ta=%d,tb=%d,M=%d,N=%d,Kc=%d,bm=%d,ns=%d,split=%d)' % (ta, tb, M, N, Kc, bm, nstage, split_k))
+    """-> the C arguments it launched with (without the stream): what a tuning.PROFILE record replays"""
+    args = cargs(int(ta), int(tb), _dt(out), a, a.stride(0), b, b.stride(0), out, out.stride(0), M, N, Kc, bias, epi, aux,
+                 aux.stride(0) if aux is not None else 0, split_k, bm, nstage, colsum_out)
+    call('goat_gemm_bf16', args, what='goat_gemm_bf16(ta=%d,tb=%d,M=%d,N=%d,Kc=%d,bm=%d,ns=%d,split=%d)' % (ta, tb, M, N, Kc, bm, nstage, split_k))
+    return args
 
 
 def _time_cfg(fn, reps=4):

@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib, tuning
-from ._plumbing import _ptr, _stream
+from ._plumbing import _ptr, _stream, launch
 from .streams import Branch
 from .tuning import BALANCED, EIGHT_WAVES, PINGPONG, USE_PP, _time_cfg, n_cu, stage_name, tile, tile_name
 
@@ -357,4 +357,4 @@ class LnReduceQueue:
             arr = (_lib.LnPartial * len(group))()
             for e, (ws, dg, db, nparts, _) in zip(arr, group):
                 e.ws, e.dgamma, e.dbeta, e.nparts = _ptr(ws), _ptr(dg), _ptr(db), nparts
-            _lib.check(_lib.lib().goat_ln_reduce_batched(_stream(), ctypes.addressof(arr), len(group), H), 'goat_ln_reduce_batched')
+            launch('goat_ln_reduce_batched', ctypes.addressof(arr), len(group), H)
