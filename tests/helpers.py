@@ -149,3 +149,62 @@ def oracle_run(cfg, sd, batch, task, autocast_bf16=False):
     loss_vec.mean().backward()
     grads = {k: v.grad for k, v in leaves.items() if torch.is_tensor(v) and v.requires_grad}
     return loss_vec.detach(), grads
+
+
+# ---- host restatement of the attention dropout mask ------------------------------------------------------------------------------
+# Source of truth: HeadRng / GoatRng / goat_thr16 in csrc/common.hpp and AttnMask in csrc/attn_tile.hpp.  Integer arithmetic only, so
+# the result is exact: the GPU tests compare the bits a kernel drew with it and build their float64 references from it.
+_M32 = np.uint64(0xFFFFFFFF)
+_MIX = np.uint64(0xD6E8FEB86659FD93)
+_GOLD = 0x9E3779B97F4A7C15
+
+
+def _mix64(x):
+    """x: uint64 array -> {x ^= x >> 32; x *= MIX} twice, then x ^= x >> 32 (mod 2^64)."""
+    s = np.uint64(32)
+    x = x ^ (x >> s)
+    x = x * _MIX
+    x = x ^ (x >> s)
+    x = x * _MIX
+    return x ^ (x >> s)
+
+
+def _mul32(x, c):
+    return (x * np.uint64(c)) & _M32
+
+
+def attn_keep_mask(dtype, seed, offset, B, nh, Lq, Lk, p):
+    """bool [B, nh, Lq, Lk]: True where goat_attn_fwd / goat_attn_bwd keep probability (b, h, q, key) under (seed, offset), `seed`
+    being the effective one (the call's seed + *rng_dev).  dtype: torch.bfloat16 (HeadRng: a 32-bit key per (b, h), one hash per pair of
+    q * Lk + key) or torch.float32 (GoatRng: one flat 64-bit counter stream from `offset`)."""
+    thr16 = np.uint64(int(np.float32(np.float32(p) * np.float32(65536.0) + np.float32(0.5))))
+    seed, offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    bh = np.arange(B * nh, dtype=np.uint64)[:, None]
+    idx = np.arange(Lq * Lk, dtype=np.uint64)[None, :]
+    with np.errstate(over='ignore'):
+        if dtype == torch.bfloat16:
+            x0 = np.uint64((seed + _GOLD * (offset + 1)) & (2 ** 64 - 1))
+            k = _mix64(x0 ^ (bh * _MIX)) & _M32
+            x = (idx >> np.uint64(1)) ^ k
+            x = _mul32(x, 0x7FEB352D)
+            x = x ^ (x >> np.uint64(15))
+            x = _mul32(x, 0x846CA68B)
+            x = x ^ (x >> np.uint64(16))
+        elif dtype == torch.float32:
+            kk = _mix64(np.array([(seed * _GOLD + 0x632BE59BD9B4E019) & (2 ** 64 - 1)], dtype=np.uint64))[0]
+            k0, k1 = kk & _M32, kk >> np.uint64(32)
+            ctr = np.uint64(offset) + bh * np.uint64(Lq * Lk) + idx
+            pair = ctr >> np.uint64(1)
+            assert int(pair.max()) < 2 ** 32, 'the __umul24 term of GoatRng::pair_bits is not restated'
+            x = pair ^ k0
+            x = x ^ (x >> np.uint64(16))
+            x = _mul32(x, 0x7FEB352D)
+            x = (x + k1) & _M32
+            x = x ^ (x >> np.uint64(15))
+            x = _mul32(x, 0x846CA68B)
+            x = x ^ (x >> np.uint64(16))
+            idx = ctr
+        else:
+            raise ValueError(dtype)
+    half = np.where((idx & np.uint64(1)) != 0, x >> np.uint64(16), x & np.uint64(0xFFFF))
+    return (half >= thr16).reshape(B, nh, Lq, Lk)
