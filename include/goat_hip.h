@@ -274,6 +274,35 @@ int goat_decode_select(void* stream, const float* logits, int64_t ld, int B, int
                        uint64_t seed, uint64_t offset, const uint64_t* rng_dev,
                        int32_t* pos_dev, int64_t* words, float* kmask, uint8_t* ended, int32_t* end_step, int32_t* n_live);
 
+/* k-means over the pooled front-door features and the draw of the FACL dictionaries (csrc/kmeans.hip): what M/utils/data.py:403-480
+ * (KMeansPicker: sklearn KMeans per modality, np.random.choice per cluster) does on the host.  Shared limits: X is [N, ld_x] in
+ * GOAT_F32 or GOAT_BF16 with N >= 1, D a multiple of 8 (>= 8), ld_x >= D, 16-byte aligned rows; 1 <= K <= 256; C is float32 [K, D],
+ * contiguous and 16-byte aligned.  GOAT_E_ARG: a null pointer that is not marked nullable, or a bad dtype; GOAT_E_SHAPE: the rest.
+ *
+ * goat_kmeans_assign: labels[i] = argmin_k (||c_k||² - 2 x_i·c_k), a tie going to the LOWEST k, a NaN score counting as +inf;
+ * mind2[i] (nullable) = max(0, ||x_i||² + that minimum); *changed (nullable) += the number of rows whose new label differs from what
+ * labels[i] held before the write.  All arithmetic is float32 (f32-input MFMA; bf16 rows are promoted, nothing is rounded to bf16). */
+int goat_kmeans_assign(void* stream, int dtype, const void* X, int64_t ld_x, const float* C,
+                       int32_t* labels, float* mind2, int32_t* changed, int N, int D, int K);
+
+/* goat_kmeans_csr: labels int32 [N] -> start int32 [K+1] (prefix sums of the cluster sizes) and order int32 [N] (row indices grouped
+ * by cluster, ascending inside each cluster: a stable counting sort).  A label outside [0, K) is skipped: start[K] < N then and the
+ * tail of `order` is not written. */
+int goat_kmeans_csr(void* stream, const int32_t* labels, int32_t* start, int32_t* order, int N, int K);
+
+/* goat_kmeans_centres: C[k] = mean of the rows X[order[start[k] .. start[k+1])], float32 accumulation in an order that depends on
+ * (order, start) alone (no atomics: two runs give the same bits).  The row of an empty cluster is left untouched. */
+int goat_kmeans_centres(void* stream, int dtype, const void* X, int64_t ld_x, const int32_t* order, const int32_t* start,
+                        float* C, int N, int D, int K);
+
+/* goat_kmeans_pick: picked[k] = order[start[k] + floor(u_k * n_k)], n_k = start[k+1] - start[k], u_k = h / 2^32 with h the 32 bits
+ * the counter hash of csrc/common.hpp gives for (seed + *rng_dev, offset + k) (rng_dev nullable), taken by multiply-high;
+ * out[b, k, :] = X[picked[k], :] for every b < B (out: [B, K, D] contiguous, the dtype of X, 16-byte aligned).  An empty cluster gives
+ * picked[k] = -1 and zero rows. */
+int goat_kmeans_pick(void* stream, int dtype, const void* X, int64_t ld_x, const int32_t* order, const int32_t* start,
+                     void* out, int32_t* picked, int N, int D, int K, int B,
+                     uint64_t seed, uint64_t offset, const uint64_t* rng_dev);
+
 /* Softmax cross-entropy (reduction none) on float32 logits [M, ld] with N valid columns (ld >= N may be padded):
  * loss[m] = logsumexp(logits[m,:N]) - logits[m,target[m]], lse saved.  Replaces F.cross_entropy on the 576 x 50265
  * MLM scores (P/model/pretrain_goat.py:213-215).  Backward writes dlogits (GOAT_BF16 or GOAT_F32) with row stride

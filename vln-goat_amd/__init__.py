@@ -4,9 +4,12 @@ Import as `vln_goat_amd` (the sibling alias package maps the importable name ont
 Contents: csrc/ (HIP kernels + C ABI), _lib.py (ctypes binding), hipops.py (autograd ops, GEMM autotuner, deferred grouped
 weight gradients), layers.py / pretrain_model.py / nav_model.py (reference-compatible nn.Module trees for pre-training
 and navigation fine-tuning), graphmap.py (host index building), dp.py (gradient arena + data-parallel engine over RCCL),
-synth.py (synthetic batches / episodes), config.py, tuned_gfx950.json (autotuned GEMM table).
+synth.py (synthetic batches / episodes), frontdoor.py (FACL dictionaries: feature TSV, device k-means, cluster pick),
+config.py, tuned_gfx950.json (autotuned GEMM table).
 """
 from .layers import compute_dtype, set_compute_dtype  # noqa: F401
 from .hipops import manual_seed  # noqa: F401
+from .frontdoor import (TIM_TSV_FIELDNAMES, DeviceKMeans, KMeansPicker, extract_front_features, read_tim_tsv,  # noqa: F401
+                        write_tim_tsv)
 
 __version__ = '0.1.0'

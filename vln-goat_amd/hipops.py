@@ -1121,6 +1121,102 @@ def decode_select(logits, state, unk, eos, pad, sampling=False, n_valid=None):
            state.pos, state.words, state.kmask, state.ended, state.end_step, state.n_live, what='goat_decode_select(B=%d,V=%d)' % (B, V))
 
 
+# ----------------------------------------------------------------------------- k-means / dictionary pick (inference only; csrc/kmeans.hip)
+KMEANS_MAXK = 256           # goat_kmeans_*: clusters
+
+
+def _kmeans_x(what, x, K):
+    """-> (N, D) of a feature table the goat_kmeans_* entry points take: float32 / bfloat16 [N, D] with dense 16-byte aligned rows."""
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[0] < 1:
+        raise ValueError('%s: x is [N, D] with dense rows and N >= 1, got %s' % (what, tuple(x.shape)))
+    N, D = x.shape
+    if D < 8 or D % 8 or not 1 <= int(K) <= KMEANS_MAXK:
+        raise ValueError('%s: D = %d must be a multiple of 8 and K = %d within 1..%d' % (what, D, K, KMEANS_MAXK))
+    if x.stride(0) < D or x.stride(0) % _epc(x) or x.data_ptr() & 15:
+        raise ValueError('%s: the rows of x must be 16-byte aligned (row stride %d)' % (what, x.stride(0)))
+    return N, D
+
+
+def _kmeans_i32(what, name, t, n, ref):
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous() or t.device != ref.device:
+        raise ValueError('%s: %s is a contiguous int32 [%d] on %s' % (what, name, n, ref.device))
+
+
+def kmeans_assign(x, centres, labels=None, mind2=None, changed=None):
+    """Nearest centre of every row (goat_kmeans_assign), exact float32: labels[i] = argmin_k ||x_i - c_k||² (ties: lowest k).
+    x [N, D] float32 / bfloat16; centres float32 [K, D] contiguous.  `labels` int32 [N] is rewritten in place when given (and *changed,
+    int32 [1], grows by the number of rows whose label moved); mind2 float32 [N] receives the squared distances.  -> (labels, mind2)."""
+    _inference_only('kmeans_assign', x, centres, labels, mind2, changed)
+    K = centres.shape[0]
+    N, D = _kmeans_x('kmeans_assign', x, K)
+    if centres.dtype != torch.float32 or tuple(centres.shape) != (K, D) or not centres.is_contiguous() or centres.device != x.device:
+        raise ValueError('kmeans_assign: centres are a contiguous float32 [K, %d] on %s' % (D, x.device))
+    if labels is None:
+        labels = torch.full((N,), -1, dtype=torch.int32, device=x.device)
+    if mind2 is None:
+        mind2 = torch.empty(N, dtype=torch.float32, device=x.device)
+    _kmeans_i32('kmeans_assign', 'labels', labels, N, x)
+    if mind2.dtype != torch.float32 or mind2.numel() != N or not mind2.is_contiguous() or mind2.device != x.device:
+        raise ValueError('kmeans_assign: mind2 is a contiguous float32 [%d] on %s' % (N, x.device))
+    if changed is not None:
+        _kmeans_i32('kmeans_assign', 'changed', changed, 1, x)
+    launch('goat_kmeans_assign', _dt(x), x, x.stride(0), centres, labels, mind2, changed, N, D, K,
+           what='goat_kmeans_assign(N=%d,D=%d,K=%d)' % (N, D, K))
+    return labels, mind2
+
+
+def kmeans_csr(labels, K):
+    """labels int32 [N] -> (start int32 [K+1], order int32 [N]): the members of cluster k are order[start[k]:start[k+1]], ascending
+    (goat_kmeans_csr, a stable counting sort on the device).  Labels outside [0, K) are skipped; the tail of `order` is -1 then."""
+    _inference_only('kmeans_csr', labels)
+    N = labels.numel()
+    if N < 1 or not 1 <= int(K) <= KMEANS_MAXK:
+        raise ValueError('kmeans_csr: N = %d >= 1 and K = %d within 1..%d' % (N, K, KMEANS_MAXK))
+    _kmeans_i32('kmeans_csr', 'labels', labels, N, labels)
+    start = torch.empty(int(K) + 1, dtype=torch.int32, device=labels.device)
+    order = torch.full((N,), -1, dtype=torch.int32, device=labels.device)
+    launch('goat_kmeans_csr', labels, start, order, N, int(K), what='goat_kmeans_csr(N=%d,K=%d)' % (N, K))
+    return start, order
+
+
+def kmeans_centres(x, order, start, centres):
+    """centres[k] = mean of the rows of cluster k (goat_kmeans_centres; float32, bitwise reproducible), in place; the row of an empty
+    cluster keeps its value.  -> centres."""
+    _inference_only('kmeans_centres', x, order, start, centres)
+    K = centres.shape[0]
+    N, D = _kmeans_x('kmeans_centres', x, K)
+    if centres.dtype != torch.float32 or tuple(centres.shape) != (K, D) or not centres.is_contiguous() or centres.device != x.device:
+        raise ValueError('kmeans_centres: centres are a contiguous float32 [K, %d] on %s' % (D, x.device))
+    _kmeans_i32('kmeans_centres', 'order', order, N, x)
+    _kmeans_i32('kmeans_centres', 'start', start, K + 1, x)
+    launch('goat_kmeans_centres', _dt(x), x, x.stride(0), order, start, centres, N, D, K,
+           what='goat_kmeans_centres(N=%d,D=%d,K=%d)' % (N, D, K))
+    return centres
+
+
+def kmeans_pick(x, order, start, out, picked=None, seed=0, offset=0, rng_dev=None):
+    """One uniformly drawn member per cluster, copied for every sample (goat_kmeans_pick): out [B, K, D] (the dtype of x, contiguous,
+    rewritten in place) gets out[b, k] = x[picked[k]]; an empty cluster gives picked[k] = -1 and zeros.  The draw is a function of
+    (seed + rng_dev[0], offset + k); rng_dev is a uint64-sized device counter (int64 [1]) or None.  -> picked int32 [K]."""
+    _inference_only('kmeans_pick', x, order, start, out, picked, rng_dev)
+    if out.dim() != 3:
+        raise ValueError('kmeans_pick: out is [B, K, D], got %s' % (tuple(out.shape),))
+    B, K, D = out.shape
+    N, Dx = _kmeans_x('kmeans_pick', x, K)
+    if Dx != D or B < 1 or out.dtype != x.dtype or not out.is_contiguous() or out.device != x.device:
+        raise ValueError('kmeans_pick: out is a contiguous %s [B >= 1, K, %d] on %s' % (x.dtype, Dx, x.device))
+    _kmeans_i32('kmeans_pick', 'order', order, N, x)
+    _kmeans_i32('kmeans_pick', 'start', start, K + 1, x)
+    if picked is None:
+        picked = torch.empty(K, dtype=torch.int32, device=x.device)
+    _kmeans_i32('kmeans_pick', 'picked', picked, K, x)
+    if rng_dev is not None and (rng_dev.dtype != torch.int64 or rng_dev.numel() != 1 or rng_dev.device != x.device):
+        raise ValueError('kmeans_pick: rng_dev is one int64 on %s' % (x.device,))
+    launch('goat_kmeans_pick', _dt(x), x, x.stride(0), order, start, out, picked, N, D, K, B, int(seed) & 0xFFFFFFFFFFFFFFFF,
+           int(offset) & 0xFFFFFFFFFFFFFFFF, rng_dev, what='goat_kmeans_pick(N=%d,D=%d,K=%d,B=%d)' % (N, D, K, B))
+    return picked
+
+
 # ----------------------------------------------------------------------------- pano fusion / gather
 class _PanoFusionFn(torch.autograd.Function):
     """fused[n] = sum_v softmax_v(tanh(x[n,v]·a + a0)) x[n,v]  (P/model/vilmodel_goat.py:354-361)."""
