@@ -173,14 +173,52 @@ def _mul32(x, c):
     return (x * np.uint64(c)) & _M32
 
 
+def _thr16(p):
+    """goat_thr16: (uint32_t)(p * 65536.0f + 0.5f) in float32"""
+    return np.uint64(int(np.float32(np.float32(p) * np.float32(65536.0) + np.float32(0.5))))
+
+
+def _goat_rng_keep(seed, ctr, thr16):
+    """GoatRng(seed).keep(ctr, thr16) for a uint64 array of counters (any shape, any parity) -> bool array of that shape."""
+    with np.errstate(over='ignore'):
+        kk = _mix64(np.array([(seed * _GOLD + 0x632BE59BD9B4E019) & (2 ** 64 - 1)], dtype=np.uint64))[0]
+        k0, k1 = kk & _M32, kk >> np.uint64(32)
+        pair = ctr >> np.uint64(1)
+        # __umul24(q >> 32, 0x9E3779): the low 24 bits of each operand, the low 32 bits of their product (zero below counter 2^33)
+        hi24 = _mul32((pair >> np.uint64(32)) & np.uint64(0xFFFFFF), 0x9E3779 & 0xFFFFFF)
+        x = (((pair & _M32) ^ k0) + hi24) & _M32
+        x = x ^ (x >> np.uint64(16))
+        x = _mul32(x, 0x7FEB352D)
+        x = (x + k1) & _M32
+        x = x ^ (x >> np.uint64(15))
+        x = _mul32(x, 0x846CA68B)
+        x = x ^ (x >> np.uint64(16))
+    half = np.where((ctr & np.uint64(1)) != 0, x >> np.uint64(16), x & np.uint64(0xFFFF))
+    return half >= thr16
+
+
+def flat_keep_mask(seed, offset, n, p):
+    """bool [n]: GoatRng(seed).keep(offset + i, goat_thr16(p)) for i < n — the mask of every row kernel of csrc/rowops.hip (dropout,
+    activation backward, LayerNorm input and output dropout), for BOTH dtypes: element i of the flat tensor owns counter offset + i
+    (mod 2^64).  `seed` is the effective one (the call's seed + *rng_dev); any offset parity, counters of any size."""
+    seed, offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+    with np.errstate(over='ignore'):
+        ctr = np.uint64(offset) + np.arange(n, dtype=np.uint64)
+    return _goat_rng_keep(seed, ctr, _thr16(p))
+
+
 def attn_keep_mask(dtype, seed, offset, B, nh, Lq, Lk, p):
     """bool [B, nh, Lq, Lk]: True where goat_attn_fwd / goat_attn_bwd keep probability (b, h, q, key) under (seed, offset), `seed`
     being the effective one (the call's seed + *rng_dev).  dtype: torch.bfloat16 (HeadRng: a 32-bit key per (b, h), one hash per pair of
-    q * Lk + key) or torch.float32 (GoatRng: one flat 64-bit counter stream from `offset`)."""
-    thr16 = np.uint64(int(np.float32(np.float32(p) * np.float32(65536.0) + np.float32(0.5))))
+    q * Lk + key) or torch.float32 (GoatRng: one flat 64-bit counter stream from `offset`, as flat_keep_mask)."""
+    thr16 = _thr16(p)
     seed, offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
     bh = np.arange(B * nh, dtype=np.uint64)[:, None]
     idx = np.arange(Lq * Lk, dtype=np.uint64)[None, :]
+    if dtype == torch.float32:
+        with np.errstate(over='ignore'):
+            ctr = np.uint64(offset) + bh * np.uint64(Lq * Lk) + idx
+        return _goat_rng_keep(seed, ctr, thr16).reshape(B, nh, Lq, Lk)
     with np.errstate(over='ignore'):
         if dtype == torch.bfloat16:
             x0 = np.uint64((seed + _GOLD * (offset + 1)) & (2 ** 64 - 1))
@@ -190,20 +228,6 @@ def attn_keep_mask(dtype, seed, offset, B, nh, Lq, Lk, p):
             x = x ^ (x >> np.uint64(15))
             x = _mul32(x, 0x846CA68B)
             x = x ^ (x >> np.uint64(16))
-        elif dtype == torch.float32:
-            kk = _mix64(np.array([(seed * _GOLD + 0x632BE59BD9B4E019) & (2 ** 64 - 1)], dtype=np.uint64))[0]
-            k0, k1 = kk & _M32, kk >> np.uint64(32)
-            ctr = np.uint64(offset) + bh * np.uint64(Lq * Lk) + idx
-            pair = ctr >> np.uint64(1)
-            assert int(pair.max()) < 2 ** 32, 'the __umul24 term of GoatRng::pair_bits is not restated'
-            x = pair ^ k0
-            x = x ^ (x >> np.uint64(16))
-            x = _mul32(x, 0x7FEB352D)
-            x = (x + k1) & _M32
-            x = x ^ (x >> np.uint64(15))
-            x = _mul32(x, 0x846CA68B)
-            x = x ^ (x >> np.uint64(16))
-            idx = ctr
         else:
             raise ValueError(dtype)
     half = np.where((idx & np.uint64(1)) != 0, x >> np.uint64(16), x & np.uint64(0xFFFF))

@@ -1342,6 +1342,10 @@ extern "C" int goat_ln_bwd_do(void* stream, int dtype, const void* dy, const voi
                               int M, int H, int accumulate, const void* dx_add, float p_out, uint64_t offset_out, void* d_post) {
   if (!dy || !z || !gamma || !mean || !rstd || !dgamma || !dbeta) return GOAT_E_ARG;
   if (M <= 0 || !(p_out >= 0.f && p_out < 1.f)) return GOAT_E_SHAPE;
+  // (in front of the clearing launch below: a refused call leaves dgamma / dbeta as they were)
+  if (dtype == GOAT_BF16) { if (int e = ln_check<bf16_t>(H)) return e; }
+  else if (dtype == GOAT_F32) { if (int e = ln_check<float>(H)) return e; }
+  else return GOAT_E_ARG;
   // deterministic mode (ws): 4-wave blocks, up to 512 per-block partial rows reduced by a second kernel (round 1).
   // atomic mode: GOAT_LN_BWD_WAVES-wave blocks (default 8) so that fewer blocks contend for the 2*H gradient words —
   // 512 four-wave blocks made the kernel 20 us instead of 12 + 5 (profiles/round2_ln_bench.txt)
