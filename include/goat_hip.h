@@ -303,6 +303,29 @@ int goat_kmeans_pick(void* stream, int dtype, const void* X, int64_t ld_x, const
                      void* out, int32_t* picked, int N, int D, int K, int B,
                      uint64_t seed, uint64_t offset, const uint64_t* rng_dev);
 
+/* Running per-slot means of picked rows: the BACL dictionaries (csrc/zdict.hip), what M/r2r/agent.py:713-848 (update_z_dict) and
+ * M/do_utils/do_intervention.py:109-148 do with per-row numpy appends and np.mean on the host.  The state is sum / comp float32 [K, D]
+ * and count int32 [K], all zero at the start; 1 <= K <= 65535, D a multiple of 8 (>= 8), sum / comp 16-byte aligned.
+ * GOAT_E_ARG: a null pointer that is not marked nullable, or a bad dtype; GOAT_E_SHAPE: the rest.
+ *
+ * goat_dict_accumulate: X is [R, ld_x] in GOAT_F32 or GOAT_BF16 (R >= 1, ld_x >= D and a multiple of the 16-byte chunk, 16-byte
+ * aligned base); rows int32 [P] (P >= 1) are row indices into X grouped by slot, slot k owning rows[start[k] .. start[k+1]) with
+ * start int32 [K+1].  The rows of a slot are added in float32 in pieces of at most 64 rows and every piece sum is folded into the
+ * pair (sum[k], comp[k]) with a compensated (two-sum) step, so that sum + comp stays accurate over any number of launches; count[k]
+ * grows by the number of rows used.  A row index outside [0, R) adds nothing and is not counted; a slot without rows in this launch
+ * keeps its pair and its count bit for bit.  No atomics: one writer per (slot, column), the order of the additions depends on the
+ * arguments alone. */
+int goat_dict_accumulate(void* stream, int dtype, const void* X, int64_t ld_x, int64_t R,
+                         const int32_t* rows, const int32_t* start,
+                         float* sum, float* comp, int32_t* count, int P, int D, int K);
+
+/* goat_dict_finish: feats[k] = (sum[k] + comp[k]) / count[k] (float32 [K, D], nullable); the same values converted to out_dtype in
+ * every out[b, k, :] (out: [B, K, D], nullable); out_pz[b, k] = count[k] / sum of all counts, formed on the device in float64 and
+ * rounded once to float32, then to out_dtype (out_pz: [B, K], nullable).  A slot with count 0 gives zeros.  feats and out are 16-byte
+ * aligned; B >= 1.  With all three outputs NULL nothing is launched. */
+int goat_dict_finish(void* stream, int out_dtype, const float* sum, const float* comp, const int32_t* count,
+                     float* feats, void* out, void* out_pz, int B, int D, int K);
+
 /* Softmax cross-entropy (reduction none) on float32 logits [M, ld] with N valid columns (ld >= N may be padded):
  * loss[m] = logsumexp(logits[m,:N]) - logits[m,target[m]], lse saved.  Replaces F.cross_entropy on the 576 x 50265
  * MLM scores (P/model/pretrain_goat.py:213-215).  Backward writes dlogits (GOAT_BF16 or GOAT_F32) with row stride

@@ -5,11 +5,14 @@ Contents: csrc/ (HIP kernels + C ABI), _lib.py (ctypes binding), hipops.py (auto
 weight gradients), layers.py / pretrain_model.py / nav_model.py (reference-compatible nn.Module trees for pre-training
 and navigation fine-tuning), graphmap.py (host index building), dp.py (gradient arena + data-parallel engine over RCCL),
 synth.py (synthetic batches / episodes), frontdoor.py (FACL dictionaries: feature TSV, device k-means, cluster pick),
+backdoor.py (BACL dictionaries: token pick plan, running means on the device, room-type image dictionary),
 config.py, tuned_gfx950.json (autotuned GEMM table).
 """
 from .layers import compute_dtype, set_compute_dtype  # noqa: F401
 from .hipops import manual_seed  # noqa: F401
 from .frontdoor import (TIM_TSV_FIELDNAMES, DeviceKMeans, KMeansPicker, extract_front_features, read_tim_tsv,  # noqa: F401
                         write_tim_tsv)
+from .backdoor import (InstrDictionaries, InstrPickPlan, build_img_zdict, img_zdict_keys, pick_positions,  # noqa: F401
+                       write_img_zdict)
 
 __version__ = '0.1.0'

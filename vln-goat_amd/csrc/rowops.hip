@@ -1253,7 +1253,7 @@ int ln_maxc(int H) {  // smallest instantiated chunk count covering H
 
 }  // namespace
 
-extern "C" int goat_version(void) { return 104; }
+extern "C" int goat_version(void) { return 105; }
 
 extern "C" int goat_ln_fwd_do(void* stream, int dtype, const void* x, const void* residual, const float* gamma,
                               const float* beta, float eps, float p, uint64_t seed, uint64_t offset,

@@ -1217,6 +1217,94 @@ def kmeans_pick(x, order, start, out, picked=None, seed=0, offset=0, rng_dev=Non
     return picked
 
 
+# ----------------------------------------------------------------------------- running per-slot means (inference only; csrc/zdict.hip)
+DICT_PIECE = 64             # goat_dict_accumulate: rows of a slot summed in plain float32 before a compensated fold
+DICT_MAXK = 65535           # goat_dict_*: slots
+
+
+class DictState:
+    """The running state of goat_dict_accumulate: sum and comp float32 [K, D] (sum + comp is the compensated total of every row a slot
+    was given), count int32 [K]."""
+
+    def __init__(self, K, D, device):
+        if not 1 <= int(K) <= DICT_MAXK or int(D) < 8 or int(D) % 8:
+            raise ValueError('DictState: K = %d within 1..%d and D = %d a multiple of 8' % (K, DICT_MAXK, D))
+        self.K, self.D = int(K), int(D)
+        self.sum = torch.zeros(self.K, self.D, dtype=torch.float32, device=device)
+        self.comp = torch.zeros(self.K, self.D, dtype=torch.float32, device=device)
+        self.count = torch.zeros(self.K, dtype=torch.int32, device=device)
+
+    def zero(self):
+        self.sum.zero_()
+        self.comp.zero_()
+        self.count.zero_()
+        return self
+
+
+def _dict_state(what, state, ref=None):
+    K, D = state.K, state.D
+    for name, t, dtype, shape in (('sum', state.sum, torch.float32, (K, D)), ('comp', state.comp, torch.float32, (K, D)),
+                                  ('count', state.count, torch.int32, (K,))):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != state.sum.device:
+            raise ValueError('%s: state.%s must be a contiguous %s %s on %s' % (what, name, dtype, list(shape), state.sum.device))
+    if ref is not None and ref.device != state.sum.device:
+        raise ValueError('%s: the state is on %s, the tensors on %s' % (what, state.sum.device, ref.device))
+    return K, D
+
+
+def dict_accumulate(x, rows, start, state):
+    """Add picked rows of x to the running per-slot sums (goat_dict_accumulate).  x: float32 / bfloat16 [R, D], possibly a strided 2-D
+    view (dense 16-byte aligned rows); rows int32 [P]: row indices into x grouped by slot; start int32 [K+1]: slot k owns
+    rows[start[k]:start[k+1]].  state (DictState) is updated in place: per launch a slot's rows are summed in float32 in pieces of
+    DICT_PIECE and folded into (sum, comp) with a compensated step; count grows by the rows used.  Indices outside [0, R) are skipped
+    and not counted.  Bitwise reproducible.  -> state."""
+    _inference_only('dict_accumulate', x, rows, start, state.sum, state.comp, state.count)
+    K, D = _dict_state('dict_accumulate', state, x)
+    if x.dim() != 2 or x.stride(1) != 1 or x.shape[0] < 1 or x.shape[1] != D:
+        raise ValueError('dict_accumulate: x is [R >= 1, %d] with dense rows, got %s' % (D, tuple(x.shape)))
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('dict_accumulate: x is float32 or bfloat16, got %s' % x.dtype)
+    R = x.shape[0]
+    if x.stride(0) < D or x.stride(0) % _epc(x) or x.data_ptr() & 15:
+        raise ValueError('dict_accumulate: the rows of x must be 16-byte aligned (row stride %d)' % x.stride(0))
+    P = rows.numel()
+    if P < 1:
+        raise ValueError('dict_accumulate: rows is empty')
+    _kmeans_i32('dict_accumulate', 'rows', rows, P, x)
+    _kmeans_i32('dict_accumulate', 'start', start, K + 1, x)
+    launch('goat_dict_accumulate', _dt(x), x, x.stride(0), R, rows, start, state.sum, state.comp, state.count, P, D, K,
+           what='goat_dict_accumulate(R=%d,D=%d,K=%d,P=%d)' % (R, D, K, P))
+    return state
+
+
+def dict_finish(state, feats=None, out=None, out_pz=None):
+    """The means and the slot probabilities of a DictState (goat_dict_finish): feats float32 [K, D] = (sum + comp) / count; the same
+    values in the dtype of `out` in every out[b] of out [B, K, D]; out_pz [B, K] (or [B, K, 1]) = count / total count, the total formed
+    on the device.  Any of the three may be None; out and out_pz share one dtype (float32 / bfloat16) and one B.  A slot that was given
+    no rows comes out as zeros."""
+    _inference_only('dict_finish', state.sum, state.comp, state.count, feats, out, out_pz)
+    K, D = _dict_state('dict_finish', state, next((t for t in (feats, out, out_pz) if t is not None), None))
+    dev = state.sum.device
+    if feats is not None and (feats.dtype != torch.float32 or tuple(feats.shape) != (K, D) or not feats.is_contiguous() or feats.device != dev):
+        raise ValueError('dict_finish: feats is a contiguous float32 [%d, %d] on %s' % (K, D, dev))
+    B, dtype = None, None
+    if out is not None:
+        if out.dim() != 3 or tuple(out.shape[1:]) != (K, D) or out.shape[0] < 1 or not out.is_contiguous() or out.device != dev:
+            raise ValueError('dict_finish: out is a contiguous [B >= 1, %d, %d] on %s, got %s' % (K, D, dev, tuple(out.shape)))
+        B, dtype = out.shape[0], out.dtype
+    if out_pz is not None:
+        shape = tuple(out_pz.shape)
+        if len(shape) not in (2, 3) or shape[0] < 1 or shape[1:] not in ((K,), (K, 1)) or not out_pz.is_contiguous() or out_pz.device != dev:
+            raise ValueError('dict_finish: out_pz is a contiguous [B >= 1, %d] or [B, %d, 1] on %s, got %s' % (K, K, dev, shape))
+        if B is not None and (shape[0] != B or out_pz.dtype != dtype):
+            raise ValueError('dict_finish: out %s %s and out_pz %s %s must share B and the dtype' % (tuple(out.shape), dtype, shape, out_pz.dtype))
+        B, dtype = shape[0], out_pz.dtype
+    if dtype is not None and dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError('dict_finish: out / out_pz are float32 or bfloat16, got %s' % dtype)
+    launch('goat_dict_finish', GOAT_BF16 if dtype == torch.bfloat16 else GOAT_F32, state.sum, state.comp, state.count, feats, out, out_pz,
+           B or 1, D, K, what='goat_dict_finish(B=%d,D=%d,K=%d)' % (B or 1, D, K))
+
+
 # ----------------------------------------------------------------------------- pano fusion / gather
 class _PanoFusionFn(torch.autograd.Function):
     """fused[n] = sum_v softmax_v(tanh(x[n,v]·a + a0)) x[n,v]  (P/model/vilmodel_goat.py:354-361)."""

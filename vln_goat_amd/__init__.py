@@ -9,5 +9,7 @@ from .layers import compute_dtype, set_compute_dtype  # noqa: E402,F401
 from .hipops import manual_seed  # noqa: E402,F401
 from .frontdoor import (TIM_TSV_FIELDNAMES, DeviceKMeans, KMeansPicker, extract_front_features, read_tim_tsv,  # noqa: E402,F401
                         write_tim_tsv)
+from .backdoor import (InstrDictionaries, InstrPickPlan, build_img_zdict, img_zdict_keys, pick_positions,  # noqa: E402,F401
+                       write_img_zdict)
 
 __version__ = '0.1.0'
