@@ -511,7 +511,7 @@ int goat_probe_tr16(void* stream, uint16_t* out);
  * NULL; float32 accumulation; y in `dtype`).  H a multiple of 8, <= 1024. */
 int goat_rowdot_fwd(void* stream, int dtype, const void* x, const float* w, const float* b, void* y, int M, int H);
 /* backward: dx[m,:] = dy[m] w (NULL: skipped); dw[H] += sum_m dy[m] x[m,:], db[1] += sum_m dy[m] (float32 atomics: the caller clears or
- * accumulates; NULL dw: both skipped). */
+ * accumulates).  NULL dw: db must be NULL too (GOAT_E_ARG otherwise: the kernel has no bias-only form). */
 int goat_rowdot_bwd(void* stream, int dtype, const void* x, const float* w, const void* dy, void* dx, float* dw, float* db, int M, int H);
 
 /* CFP fused vector (P/model/pretrain_goat.py:486-499 with the glocal fusion weight of :393-399): w = sigmoid(fwl[b]) (fwl: the

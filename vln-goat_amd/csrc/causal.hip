@@ -756,6 +756,7 @@ extern "C" int goat_rowdot_fwd(void* stream, int dtype, const void* x, const flo
 extern "C" int goat_rowdot_bwd(void* stream, int dtype, const void* x, const float* w, const void* dy, void* dx, float* dw, float* db, int M,
                                int H) {
   if (!x || !w || !dy) return GOAT_E_ARG;
+  if (db && !dw) return GOAT_E_ARG;          // (the kernel adds db behind the dw partials: a bias gradient alone would be dropped silently)
   if (M <= 0 || H <= 0 || (H % 8)) return GOAT_E_SHAPE;
   if (!dx && !dw) return 0;
   int blocks = (M + 3) / 4;
