@@ -471,6 +471,48 @@ int goat_adamw_step(void* stream, const float* grad_arena, float* exp_avg, float
                     const int32_t* chunks, int nchunks, float beta1, float beta2, float eps, float max_norm,
                     const float* sq_norm);
 
+/* ---- the fine-tuning update on the gradient arena (SURVEY a-19, config 4) ------------------------------------------------------
+ * The reference's iteration ends with optim_step (M/r2r/agent.py:414-420; M/r2r/agent_base.py:105-123 build, :160-200 loop):
+ * clip_grad_norm_(vln_bert.parameters(), 40.) and torch.optim.{AdamW | Adam | RMSprop | SGD}(params, lr = args.lr).step() with torch's
+ * default hyper-parameters, optionally under a learning-rate schedule (agent_base.py:125-128); the optimizer state is saved / resumed
+ * with --save_optimizer / --resume_optimizer (agent_base.py:205-253).  g = gradient * clip coefficient; torch's single-tensor forms:
+ *   GOAT_OPT_ADAMW   : p *= 1 - lr*wd;  m = lerp(m, g, 1-b1);  v = b2 v + (1-b2) g^2;  p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+ *                      with bc1 = 1 - b1^t, bc2 = 1 - b2^t, t = *step + 1                (torch defaults: 0.9 / 0.999, 1e-8, wd 1e-2)
+ *   GOAT_OPT_ADAM    : the same without the first line; wd != 0 (default 0): g += wd*p before the moments
+ *   GOAT_OPT_RMSPROP : v = a v + (1-a) g^2;  p -= lr * g / (sqrt(v) + eps)                (a = hyper->beta1; 0.99, 1e-8; v = exp_avg_sq)
+ *   GOAT_OPT_SGD     : p -= lr * g                                                        (wd as for Adam in both)
+ * One launch over the chunk table of goat_adamw_step (chunk c = {tensor index, first element}, <= 65536 elements), 16-byte accesses
+ * where the addresses allow, the operand copies (shadow0 / shadow1 bf16, shadow_f32, the cols / ld0 row-padded form) refreshed in the
+ * same pass at their addresses.  EVERYTHING that changes from step to step is read from device memory — `hyper` (doubles: 1 - b^t,
+ * lr / bc1 and 1 - lr*wd are formed in double and rounded to float once, as torch forms them on the host), the int64 counter `step`
+ * (= completed steps) and the squared norm goat_grad_sqnorm accumulated into *sq_norm — so the step can be part of a captured
+ * hipGraph: a replay picks up a new learning rate or gradient without a host argument.  Clip coefficient as in goat_adamw_step,
+ * min(1, max_norm / (sqrt(*sq_norm) + 1e-6)); hyper->max_norm <= 0: no clipping.  exp_avg may be NULL for RMSprop / SGD, exp_avg_sq
+ * for SGD.
+ *   goat_optim_advance : the step's stream-ordered tail, ONE thread: *step += 1, *last_sq = *sq_norm, *sq_norm = 0 (the next
+ *                        goat_grad_sqnorm accumulates from zero).  The update kernel's workgroups all read these and never write them. */
+#define GOAT_OPT_ADAMW 0
+#define GOAT_OPT_ADAM 1
+#define GOAT_OPT_RMSPROP 2
+#define GOAT_OPT_SGD 3
+typedef struct goat_optim_tensor {
+  float* param;            /* float32 master weights */
+  void* shadow0;           /* bf16 copy, same element order (or the row-padded image when cols > 0), or NULL */
+  void* shadow1;           /* second bf16 copy, or NULL */
+  float* shadow_f32;       /* float32 copy, same element order, or NULL */
+  int64_t arena_off;       /* first element of this tensor in the gradient / moment arenas */
+  int64_t numel;
+  int32_t cols;            /* > 0: shadow0 is a row-padded image — element i goes to (i / cols) * ld0 + i % cols */
+  int32_t ld0;
+} goat_optim_tensor;
+typedef struct goat_optim_hyper {
+  double lr, beta1, beta2, eps, weight_decay, max_norm;      /* beta1 = alpha for RMSprop */
+} goat_optim_hyper;
+int goat_optim_step(void* stream, int algo, const float* grad_arena, float* exp_avg, float* exp_avg_sq,
+                    const goat_optim_tensor* tensors, const int32_t* chunks, int nchunks, const goat_optim_hyper* hyper,
+                    const int64_t* step, const float* sq_norm);
+int goat_optim_advance(void* stream, int64_t* step, float* sq_norm, float* last_sq);
+
 /* Tail of the single-action-prediction head, one launch per direction (csrc/causal.hip).  gs [B,G] / ls [B,W]: raw scores of the
  * global / local heads (dtype GOAT_BF16 | GOAT_F32); fwl [B]: fusion logit (fw = sigmoid(fwl) when fw_sigmoid, fwl itself otherwise;
  * NULL: fw = 0.5).  Masks (bytes, any may be NULL): gvis 1 = visited, gvalid 0 = beyond the map, glens map lengths, lmask 1 = masked

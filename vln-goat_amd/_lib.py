@@ -76,6 +76,8 @@ SIGNATURES = {
     'goat_wgrad_balanced_ws_bytes': [_i32],
     'goat_grad_sqnorm': [_vp, _vp, _vp, _i32, _vp],
     'goat_adamw_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _vp],
+    'goat_optim_step': [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],
+    'goat_optim_advance': [_vp, _vp, _vp, _vp],
     'goat_sap_fuse_fwd': [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32],
     'goat_sap_fuse_bwd': [_vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32],
     'goat_infonce_fwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32],
@@ -101,6 +103,21 @@ class AdamwTensor(ctypes.Structure):
     _fields_ = [('param', ctypes.c_void_p), ('shadow0', ctypes.c_void_p), ('shadow1', ctypes.c_void_p), ('arena_off', ctypes.c_int64),
                 ('numel', ctypes.c_int64), ('step_size', ctypes.c_float), ('decay', ctypes.c_float), ('shadow_f32', ctypes.c_void_p),
                 ('cols', ctypes.c_int32), ('ld0', ctypes.c_int32)]
+
+
+class OptimTensor(ctypes.Structure):
+    """struct goat_optim_tensor (include/goat_hip.h)."""
+    _fields_ = [('param', ctypes.c_void_p), ('shadow0', ctypes.c_void_p), ('shadow1', ctypes.c_void_p), ('shadow_f32', ctypes.c_void_p),
+                ('arena_off', ctypes.c_int64), ('numel', ctypes.c_int64), ('cols', ctypes.c_int32), ('ld0', ctypes.c_int32)]
+
+
+class OptimHyper(ctypes.Structure):
+    """struct goat_optim_hyper (include/goat_hip.h)."""
+    _fields_ = [('lr', ctypes.c_double), ('beta1', ctypes.c_double), ('beta2', ctypes.c_double), ('eps', ctypes.c_double),
+                ('weight_decay', ctypes.c_double), ('max_norm', ctypes.c_double)]
+
+
+OPT_ADAMW, OPT_ADAM, OPT_RMSPROP, OPT_SGD = 0, 1, 2, 3
 
 
 class WgradProblem(ctypes.Structure):

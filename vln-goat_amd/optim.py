@@ -10,17 +10,90 @@ Here the gradients already sit in ONE float32 buffer (dp.GradArena); the moments
 whole update is two kernels (goat_grad_sqnorm, goat_adamw_step in csrc/optim.hip) that also refresh the bf16 operand
 "shadows" of the weights, so the next forward needs no cast kernels.  No host synchronisation: the clip coefficient is
 computed on the device; `last_grad_norm()` reads it back on request.
+
+Fine-tuning (M = the reference's map_nav_src) ends its iteration with another update — FusedTorchOptim below:
+  * M/r2r/agent_base.py:105-123    torch.optim.{RMSprop | Adam | AdamW | SGD}(vln_bert.parameters(), lr=args.lr), torch's defaults; a second
+                                   optimizer of the same class over the critic
+  * M/r2r/agent_base.py:191-200    loss.backward(); clip_grad_norm_(vln_bert.parameters(), 40.); both .step(); the lr schedule's .step()
+  * M/r2r/agent_base.py:205-253    optimizer.state_dict() saved / loaded with the checkpoint (--save_optimizer / --resume_optimizer)
 """
 import ctypes
 
 import torch
 
 from . import _lib
-from ._plumbing import launch
+from ._plumbing import _ptr, launch
 from .shadows import BPAD, CAT, CATB, PLAIN, ROWPAD, key_kind, member_ids
 
 NO_DECAY = ('bias', 'LayerNorm.bias', 'LayerNorm.weight')      # P/optim/misc.py:13
 CHUNK = 65536
+
+
+def _copies(plist):
+    """Which cached operand copies the update kernel refreshes itself.  -> ({id(p): slots}, done) with slots =
+    {'s0', 's1': bf16 pointers in the parameter's element order, 'cols', 'ld0': s0 is a row-padded image, 'f32': float32
+    pointer} and done = the storage addresses of the copies that are COMPLETELY covered by the slots handed out (a
+    concatenated copy only when each of its members got one).  Everything else is rebuilt in place after the kernel by
+    hipops.refresh_shadows — a cached copy is never dropped: a captured hipGraph may read it at its address.
+    (Key layouts: the table at the top of shadows.py.)"""
+    by_id = {id(p): p for p in plist}
+    slots = {id(p): {'bf16': [], 'pad': None, 'f32': None} for p in plist}
+    whole = []            # (tensor, [(param id, kind, pointer)]) per cached copy
+    for p in plist:
+        cache = p.__dict__.get('_goat_shadow')
+        if not cache:
+            continue
+        for k, (ver, t) in cache.items():
+            if not t.is_contiguous():
+                continue
+            kd = key_kind(k)
+            if kd == CAT:
+                if k[1] != torch.bfloat16 or k[2] or any(i not in by_id for i in member_ids(k)):
+                    continue
+                row, members = 0, []
+                for i in member_ids(k):
+                    members.append((i, 'bf16', t.data_ptr() + row * t.shape[1] * 2))
+                    row += by_id[i].shape[0]
+                whole.append((t, members))
+            elif kd == CATB:
+                if t.dtype != torch.float32 or any(i not in by_id for i in member_ids(k)):
+                    continue
+                off, members = 0, []
+                for i in member_ids(k):
+                    members.append((i, 'f32', t.data_ptr() + off * 4))
+                    off += by_id[i].numel()
+                whole.append((t, members))
+            elif kd == ROWPAD:
+                if t.dtype == torch.bfloat16 and t.shape[1:] == p.shape[1:] and t.shape[0] >= p.shape[0]:
+                    whole.append((t, [(id(p), 'bf16', t.data_ptr())]))
+            elif kd == BPAD:          # zero-padded float32 image of a bias: the leading numel(p) floats are the bias
+                if t.dtype == torch.float32 and t.numel() >= p.numel():
+                    whole.append((t, [(id(p), 'f32', t.data_ptr())]))
+            elif kd == PLAIN and k[0] == torch.bfloat16 and k[1] is False and t.dtype == torch.bfloat16:
+                if k[2] == 0:
+                    whole.append((t, [(id(p), 'bf16', t.data_ptr())]))
+                elif p.dim() == 2:
+                    whole.append((t, [(id(p), 'pad', (t.data_ptr(), p.shape[1], p.shape[1] + k[2]))]))
+    done = set()
+    for t, members in whole:
+        ok = True
+        for i, kind, _ in members:        # does every member still have a free slot of that kind?
+            sl = slots[i]
+            if kind == 'bf16':
+                ok &= len(sl['bf16']) < (1 if sl['pad'] is not None else 2)
+            elif kind == 'pad':
+                ok &= sl['pad'] is None and len(sl['bf16']) < 2
+            else:
+                ok &= sl['f32'] is None
+        if not ok:
+            continue
+        for i, kind, ptr in members:
+            if kind == 'bf16':
+                slots[i]['bf16'].append(ptr)
+            else:
+                slots[i][kind] = ptr
+        done.add(t.data_ptr())
+    return slots, done
 
 
 class FusedAdamW:
@@ -82,70 +155,7 @@ class FusedAdamW:
         return pl
 
     def _copies(self, plist):
-        """Which cached operand copies the update kernel refreshes itself.  -> ({id(p): slots}, done) with slots =
-        {'s0', 's1': bf16 pointers in the parameter's element order, 'cols', 'ld0': s0 is a row-padded image, 'f32': float32
-        pointer} and done = the storage addresses of the copies that are COMPLETELY covered by the slots handed out (a
-        concatenated copy only when each of its members got one).  Everything else is rebuilt in place after the kernel by
-        hipops.refresh_shadows — a cached copy is never dropped: a captured hipGraph may read it at its address.
-        (Key layouts: the table at the top of shadows.py.)"""
-        by_id = {id(p): p for p in plist}
-        slots = {id(p): {'bf16': [], 'pad': None, 'f32': None} for p in plist}
-        whole = []            # (tensor, [(param id, kind, pointer)]) per cached copy
-        for p in plist:
-            cache = p.__dict__.get('_goat_shadow')
-            if not cache:
-                continue
-            for k, (ver, t) in cache.items():
-                if not t.is_contiguous():
-                    continue
-                kd = key_kind(k)
-                if kd == CAT:
-                    if k[1] != torch.bfloat16 or k[2] or any(i not in by_id for i in member_ids(k)):
-                        continue
-                    row, members = 0, []
-                    for i in member_ids(k):
-                        members.append((i, 'bf16', t.data_ptr() + row * t.shape[1] * 2))
-                        row += by_id[i].shape[0]
-                    whole.append((t, members))
-                elif kd == CATB:
-                    if t.dtype != torch.float32 or any(i not in by_id for i in member_ids(k)):
-                        continue
-                    off, members = 0, []
-                    for i in member_ids(k):
-                        members.append((i, 'f32', t.data_ptr() + off * 4))
-                        off += by_id[i].numel()
-                    whole.append((t, members))
-                elif kd == ROWPAD:
-                    if t.dtype == torch.bfloat16 and t.shape[1:] == p.shape[1:] and t.shape[0] >= p.shape[0]:
-                        whole.append((t, [(id(p), 'bf16', t.data_ptr())]))
-                elif kd == BPAD:          # zero-padded float32 image of a bias: the leading numel(p) floats are the bias
-                    if t.dtype == torch.float32 and t.numel() >= p.numel():
-                        whole.append((t, [(id(p), 'f32', t.data_ptr())]))
-                elif kd == PLAIN and k[0] == torch.bfloat16 and k[1] is False and t.dtype == torch.bfloat16:
-                    if k[2] == 0:
-                        whole.append((t, [(id(p), 'bf16', t.data_ptr())]))
-                    elif p.dim() == 2:
-                        whole.append((t, [(id(p), 'pad', (t.data_ptr(), p.shape[1], p.shape[1] + k[2]))]))
-        done = set()
-        for t, members in whole:
-            ok = True
-            for i, kind, _ in members:        # does every member still have a free slot of that kind?
-                sl = slots[i]
-                if kind == 'bf16':
-                    ok &= len(sl['bf16']) < (1 if sl['pad'] is not None else 2)
-                elif kind == 'pad':
-                    ok &= sl['pad'] is None and len(sl['bf16']) < 2
-                else:
-                    ok &= sl['f32'] is None
-            if not ok:
-                continue
-            for i, kind, ptr in members:
-                if kind == 'bf16':
-                    slots[i]['bf16'].append(ptr)
-                else:
-                    slots[i][kind] = ptr
-            done.add(t.data_ptr())
-        return slots, done
+        return _copies(plist)
 
     def step(self, task=None, max_norm=5.0):
         """clip_grad_norm_(max_norm) + AdamW on the parameters `task` uses (all arena parameters if None)."""
@@ -211,3 +221,269 @@ def build_optimizer(model, opts, arena):
     if getattr(opts, 'optim', 'adamw') != 'adamw':
         raise ValueError('invalid optimizer')
     return FusedAdamW(model.named_parameters(), arena, lr=opts.learning_rate, betas=tuple(opts.betas), weight_decay=opts.weight_decay)
+
+
+# ---------------------------------------------------------------------------------------------------------------- fine-tuning
+_TORCH_OPTIM = {'rms': ('RMSprop', _lib.OPT_RMSPROP), 'adam': ('Adam', _lib.OPT_ADAM), 'adamW': ('AdamW', _lib.OPT_ADAMW),
+                'sgd': ('SGD', _lib.OPT_SGD)}                                      # args.optim, M/r2r/agent_base.py:108-117
+_MOMENTS = {_lib.OPT_ADAMW: ('exp_avg', 'exp_avg_sq'), _lib.OPT_ADAM: ('exp_avg', 'exp_avg_sq'), _lib.OPT_RMSPROP: ('square_avg',),
+            _lib.OPT_SGD: ()}                                                      # torch's state keys, in torch's order after 'step'
+_UNSUPPORTED = ('momentum', 'centered', 'amsgrad', 'nesterov', 'dampening', 'maximize', 'capturable', 'differentiable')
+
+
+class FusedTorchOptim:
+    """torch.optim.{RMSprop | Adam | AdamW | SGD} + clip_grad_norm_ on the parameters of a dp.GradArena that `task` uses: the update
+    the reference's fine-tuning iteration ends with (M/r2r/agent_base.py:105-123, 191-200).
+
+        opt = FusedTorchOptim(vln_bert.named_parameters(), arena, algo=args.optim, lr=args.lr)
+        ... the iteration's backward passes (gradients in the 'nav' arena) ...
+        opt.step(max_norm=40.0)             # goat_grad_sqnorm, goat_optim_step, goat_optim_advance: three launches
+
+    One parameter group with torch's keys (`param_groups[0]`), torch's formulas and defaults, torch's state_dict format.  Everything
+    a step reads that changes between steps lives in device memory (learning rate and the other hyper-parameters, the step counter, the
+    gradient norm), so `step()` inside `hipops.graph(g)` records device work only: between replays, `set_lr(x)` is the schedule.
+    Parameters outside the arena (unused, frozen, requires_grad=False) are never touched and have no state."""
+
+    def __init__(self, named_params, arena, algo='adamW', lr=1e-5, task='nav', **torch_defaults):
+        if algo not in _TORCH_OPTIM:
+            raise ValueError('invalid optimizer %r (rms | adam | adamW | sgd)' % (algo,))
+        cls_name, self.algo = _TORCH_OPTIM[algo]
+        self.torch_class = getattr(torch.optim, cls_name)
+        # torch validates the hyper-parameters and supplies its defaults and group keys: the group of the installed torch, minus 'params'
+        group = dict(self.torch_class([torch.nn.Parameter(torch.zeros(1))], lr=lr, **torch_defaults).param_groups[0])
+        for k in _UNSUPPORTED:
+            if group.get(k):
+                raise ValueError('FusedTorchOptim(%s): %s=%r is not implemented' % (algo, k, group[k]))
+        if group.get('fused') or (self.algo != _lib.OPT_ADAMW and group.get('decoupled_weight_decay')):
+            raise ValueError('FusedTorchOptim(%s): fused / decoupled_weight_decay are not options of this class' % algo)
+        group.pop('params')
+        self.arena, self.task = arena, task
+        named = list(named_params)
+        self.all_params = [p for _, p in named]                     # the order state_dict() indexes by
+        key = task.split('_')[0] if task is not None else None
+        covered = {id(p) for _, p in named if id(p) in arena.views and (arena.tasks_of[id(p)] is None or key is None or key in arena.tasks_of[id(p)])}
+        self.params = [p for p in arena.params if id(p) in covered]             # arena order: the kernel's tensor table
+        self.names = {id(p): n for n, p in named if id(p) in covered}
+        self._by_id = {id(p): p for p in self.params}
+        group['params'] = self.all_params
+        self.param_groups = [group]
+        dev = arena.flat.device
+        self._cuda = dev.type == 'cuda'
+        nm = len(_MOMENTS[self.algo])
+        self.exp_avg = torch.zeros_like(arena.flat) if nm == 2 else None
+        self.exp_avg_sq = torch.zeros_like(arena.flat) if nm >= 1 else None      # (RMSprop's square_avg)
+        self._t = torch.zeros(1, dtype=torch.int64, device=dev)                 # completed steps, shared by every covered parameter
+        self._norm = torch.zeros(2, dtype=torch.float32, device=dev)            # [squared norm being accumulated, that of the last step]
+        self._hyper = torch.zeros(6, dtype=torch.float64, device=dev)           # struct goat_optim_hyper
+        self._hyper_pinned = torch.zeros(6, dtype=torch.float64).pin_memory() if self._cuda else None
+        self._hyper_host, self._hyper_copied = None, None
+        self._max_norm = 40.0
+        chunks, rng = [], []
+        for i, p in enumerate(self.params):
+            for first in range(0, p.numel(), CHUNK):
+                chunks += [i, first]
+            a = arena.offsets[id(p)]
+            rng += [a, a + p.numel()]        # the norm runs over the parameters' own elements (alignment padding is never written)
+        self._chunks = torch.tensor(chunks, dtype=torch.int32, device=dev)
+        self._nchunks = len(chunks) // 2
+        self._ranges = torch.tensor(rng, dtype=torch.int64, device=dev)
+        nbytes = max(1, len(self.params)) * ctypes.sizeof(_lib.OptimTensor)
+        self._table_host = (_lib.OptimTensor * max(1, len(self.params)))()
+        self._table = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self._table_pinned = torch.zeros(nbytes, dtype=torch.uint8).pin_memory() if self._cuda else None
+        self._table_sig, self._table_copied, self._done, self._keep = None, None, set(), []
+        self.last_refreshed = 0
+        self._upload_hyper()
+        self._build_table()
+
+    # -- the device-resident hyper-parameters ----------------------------------------------------------------------------------------
+    def _hyper_values(self):
+        g = self.param_groups[0]
+        if self.algo in (_lib.OPT_ADAMW, _lib.OPT_ADAM):
+            b1, b2 = g['betas']
+        else:
+            b1, b2 = g.get('alpha', 0.0), 0.0
+        mn = self._max_norm
+        return (float(g['lr']), float(b1), float(b2), float(g.get('eps', 0.0)), float(g['weight_decay']), float(mn) if mn is not None and mn > 0 else 0.0)
+
+    def _upload_hyper(self):
+        """param_groups[0] (and the clip norm) -> the device block, when they changed: pinned and stream-ordered, so a replay launched after
+        this call reads the new values and one launched before it the old ones.  Never inside a capture."""
+        vals = self._hyper_values()
+        if vals == self._hyper_host:
+            return
+        if self._cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedTorchOptim: hyper-parameters changed inside a hipGraph capture (%r -> %r); call set_lr() / step() with '
+                               'these values once before capturing — a captured step reads them from device memory' % (self._hyper_host, vals))
+        new = torch.tensor(vals, dtype=torch.float64)
+        if self._cuda:
+            if self._hyper_copied is not None:
+                self._hyper_copied.synchronize()        # the previous upload has read the pinned block
+            self._hyper_pinned.copy_(new)
+            self._hyper.copy_(self._hyper_pinned, non_blocking=True)
+            self._hyper_copied = torch.cuda.Event()
+            self._hyper_copied.record()
+        else:
+            self._hyper.copy_(new)
+        self._hyper_host = vals
+
+    def set_lr(self, lr):
+        """The schedule's step between replays of a captured iteration: lr may be a number or a callable of the current learning rate
+        (lr_scheduler-style lambdas take the step; use a closure for that)."""
+        g = self.param_groups[0]
+        g['lr'] = float(lr(g['lr'])) if callable(lr) else float(lr)
+        self._upload_hyper()
+
+    # -- the tensor table: parameters, arena offsets, the cached copies the kernel refreshes itself ---------------------------------
+    def _signature(self):
+        sig = []
+        for p in self.params:
+            cache = p.__dict__.get('_goat_shadow')
+            if cache:
+                sig.append((id(p), tuple((k, t.data_ptr()) for k, (_, t) in cache.items())))
+        return tuple(sig)
+
+    def _build_table(self):
+        """Once, and again only when the set of cached copies changed (a new operand dtype, a first bf16 pass).  Never inside a capture:
+        there the table in use stays, and the copies it does not cover are rebuilt by refresh_shadows (device work, captured)."""
+        sig = self._signature()
+        if sig == self._table_sig:
+            return
+        if self._cuda and torch.cuda.is_current_stream_capturing():
+            return
+        slots, done = _copies(self.params)
+        host, arena = self._table_host, self.arena
+        for i, p in enumerate(self.params):
+            sl, e = slots[id(p)], host[i]
+            e.param, e.arena_off, e.numel = p.data_ptr(), arena.offsets[id(p)], p.numel()
+            bf = list(sl['bf16'])
+            if sl['pad'] is not None:
+                e.shadow0, e.cols, e.ld0 = sl['pad']
+                e.shadow1 = bf[0] if bf else None
+            else:
+                e.cols, e.ld0 = 0, 0
+                e.shadow0 = bf[0] if len(bf) > 0 else None
+                e.shadow1 = bf[1] if len(bf) > 1 else None
+            e.shadow_f32 = sl['f32']
+        nbytes = ctypes.sizeof(host)
+        raw = torch.frombuffer((ctypes.c_uint8 * nbytes).from_address(ctypes.addressof(host)), dtype=torch.uint8)
+        if self._cuda:
+            if self._table_copied is not None:
+                self._table_copied.synchronize()
+            self._table_pinned.copy_(raw)
+            self._table.copy_(self._table_pinned, non_blocking=True)
+            self._table_copied = torch.cuda.Event()
+            self._table_copied.record()
+        else:
+            self._table.copy_(raw)
+        # the table holds raw addresses: the copies it names stay alive as long as it is in use
+        self._keep = [t for p in self.params for _, t in (p.__dict__.get('_goat_shadow') or {}).values()]
+        self._table_sig, self._done = sig, done
+
+    def step(self, max_norm=40.0):
+        """clip_grad_norm_(max_norm) + the update of `algo` on the covered parameters; max_norm None or <= 0: no clipping."""
+        from . import hipops
+        if not self.params:
+            return
+        self._max_norm = max_norm
+        self._upload_hyper()
+        self._build_table()
+        arena = self.arena
+        launch('goat_grad_sqnorm', arena.flat, self._ranges, len(self.params), self._norm)
+        launch('goat_optim_step', self.algo, arena.flat, self.exp_avg, self.exp_avg_sq, self._table, self._chunks, self._nchunks, self._hyper,
+               self._t, self._norm)
+        launch('goat_optim_advance', self._t, self._norm, _ptr(self._norm, 1))
+        # the copies the kernel did not cover (transposed / float32 images of the parity mode, a third bf16 copy): same storage, new values
+        by_id, done = self._by_id, self._done
+        self.last_refreshed = sum(hipops.refresh_shadows(p, by_id, done) for p in self.params)
+
+    def last_grad_norm(self):
+        """total gradient norm of the last step() (synchronises)."""
+        return float(self._norm[1].sqrt().item())
+
+    def steps_done(self):
+        """the device counter (synchronises)."""
+        return int(self._t.item())
+
+    def _moments_of(self, p):
+        a = self.arena.offsets[id(p)]
+        bufs = (self.exp_avg, self.exp_avg_sq) if self.algo in (_lib.OPT_ADAMW, _lib.OPT_ADAM) else (self.exp_avg_sq,)
+        return {k: b[a:a + p.numel()].view_as(p) for k, b in zip(_MOMENTS[self.algo], bufs)}
+
+    def state_of(self, p):
+        """{'step', moments as views into the moment arenas} of a covered parameter (synchronises for the step)."""
+        st = {'step': self.steps_done()}
+        st.update(self._moments_of(p))
+        return st
+
+    # -- torch's optimizer checkpoint format (M/r2r/agent_base.py:205-253 saves / loads optimizer.state_dict()) ----------------------
+    def state_dict(self):
+        """What torch.optim.<X>(params).state_dict() returns after the same steps: state keyed by the index of the parameter in the
+        `named_params` order, entries only for the stepped (covered) parameters, 'step' as the installed torch writes it (a float32
+        scalar tensor from 1.12 on, an int before), moments as copies — a view would drag the whole moment arena into torch.save."""
+        t = self.steps_done()
+        step_as_tensor = tuple(int(x) for x in torch.__version__.split('+')[0].split('.')[:2]) >= (1, 12)
+        state = {}
+        if t > 0 and self.algo != _lib.OPT_SGD:
+            for i, p in enumerate(self.all_params):
+                if id(p) in self._by_id:
+                    ent = {'step': torch.tensor(float(t), dtype=torch.float32) if step_as_tensor else t}
+                    ent.update({k: v.clone() for k, v in self._moments_of(p).items()})
+                    state[i] = ent
+        group = {k: v for k, v in self.param_groups[0].items() if k != 'params'}
+        group['params'] = list(range(len(self.all_params)))
+        return {'state': state, 'param_groups': [group]}
+
+    def load_state_dict(self, sd):
+        """A checkpoint of torch's optimizer over the same parameter list (or state_dict() of this class).  'step' an int (torch 1.9) or
+        a tensor, moments on any device.  Refused: another number of parameters, a moment of another shape, steps that differ among
+        the covered parameters (this class keeps ONE counter).  Entries of parameters outside the arena are ignored."""
+        groups = sd['param_groups']
+        if len(groups) != 1 or len(groups[0]['params']) != len(self.all_params):
+            raise ValueError('loaded state dict has %d parameter group(s) / %d parameters, this optimizer one group of %d'
+                             % (len(groups), len(groups[0]['params']) if groups else 0, len(self.all_params)))
+        state, keys = sd['state'], _MOMENTS[self.algo]
+        steps, loads = set(), []
+        for i, p in enumerate(self.all_params):
+            if id(p) not in self._by_id:
+                continue
+            ent = state.get(groups[0]['params'][i])
+            if not ent or (not keys and 'step' not in ent):
+                steps.add(0)
+                continue
+            stp = ent.get('step', 0)
+            steps.add(int(round(float(stp.item() if torch.is_tensor(stp) else stp))))
+            for k in keys:
+                if k not in ent:
+                    raise ValueError('state of parameter %d (%s) has no %r' % (i, self.names[id(p)], k))
+                if tuple(ent[k].shape) != tuple(p.shape):
+                    raise ValueError('state %r of parameter %d (%s) has shape %s, the parameter %s'
+                                     % (k, i, self.names[id(p)], tuple(ent[k].shape), tuple(p.shape)))
+                loads.append((p, k, ent[k]))
+        if self.algo == _lib.OPT_SGD:
+            steps = {0}                       # (torch's SGD without momentum keeps no state)
+        if len(steps) > 1:
+            raise ValueError('the covered parameters were stepped a different number of times (%s): one counter cannot hold that' % sorted(steps))
+        old = self.param_groups[0]
+        new = {k: v for k, v in groups[0].items() if k != 'params'}
+        for k in _UNSUPPORTED:
+            if new.get(k):
+                raise ValueError('loaded parameter group has %s=%r: not implemented' % (k, new[k]))
+        old.update(new)
+        for buf in (self.exp_avg, self.exp_avg_sq):
+            if buf is not None:
+                buf.zero_()
+        for p, k, v in loads:
+            self._moments_of(p)[k].copy_(v.detach().to(torch.float32))
+        self._t.fill_(steps.pop() if steps else 0)
+        self._upload_hyper()
+
+
+def build_nav_optimizers(args, vln_bert, critic, arena):
+    """M/r2r/agent_base.py:107-123 on the arena: (FusedTorchOptim over vln_bert, torch's optimizer of args.optim over the critic's
+    parameters), both with lr = args.lr and torch's defaults.  The critic never receives a gradient (train_rl is off upstream), so
+    torch's step skips every one of its parameters."""
+    if args.optim not in _TORCH_OPTIM:
+        raise ValueError('invalid optimizer %r' % (args.optim,))
+    opt = FusedTorchOptim(vln_bert.named_parameters(), arena, algo=args.optim, lr=args.lr)
+    return opt, getattr(torch.optim, _TORCH_OPTIM[args.optim][0])(critic.parameters(), lr=args.lr)
