@@ -453,7 +453,10 @@ int goat_dict_wsum_bwd(void* stream, int dtype_dout, const void* dout, const flo
  *                      scalar goat_grad_sqnorm produced (max_norm <= 0: no clipping), so the step needs no host
  *                      synchronisation.  shadow0 / shadow1 / shadow_f32 (optional): the copies of the parameter the GEMMs read
  *                      (bf16 operand "shadows", the float32 image inside a concatenated QKV bias) refreshed in the same
- *                      pass AT THEIR ADDRESSES — a captured hipGraph that reads them sees the updated weights. */
+ *                      pass AT THEIR ADDRESSES — a captured hipGraph that reads them sees the updated weights.  16-byte
+ *                      accesses where every address of the tensor allows (gradient, moments, parameter, copies), scalar
+ *                      ones elsewhere; a chunk whose first element lies outside its tensor is skipped.  (Both as in
+ *                      goat_optim_step below: the two kernels share one walk over the chunk.) */
 typedef struct goat_adamw_tensor {
   float* param;            /* float32 master weights */
   void* shadow0;           /* bf16 copy, same element order, or NULL */

@@ -74,7 +74,7 @@ def _setup():
             hipops.refresh_shadows(p, by_id)
 
     info = {'device': torch.cuda.get_device_name(0), 'tensors': len(params), 'elements': int(sum(p.numel() for p in params)),
-            'chunks': fused._nchunks, 'copies': int(sum(len(p.__dict__.get('_goat_shadow') or {}) for p in params))}
+            'chunks': fused._tb.nchunks, 'copies': int(sum(len(p.__dict__.get('_goat_shadow') or {}) for p in params))}
     return torch, hipops, fused, form_a, form_c, info
 
 

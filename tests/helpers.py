@@ -1,4 +1,5 @@
 """Shared test helpers: golden cases, oracle runs, gradient fingerprints."""
+import math
 import os
 import sys
 
@@ -149,6 +150,47 @@ def oracle_run(cfg, sd, batch, task, autocast_bf16=False):
     loss_vec.mean().backward()
     grads = {k: v.grad for k, v in leaves.items() if torch.is_tensor(v) and v.requires_grad}
     return loss_vec.detach(), grads
+
+
+# ---- host restatement of the pre-training update ---------------------------------------------------------------------------------
+# clip_grad_norm_(max_norm) + the reference's AdamW (P/optim/adamw.py:53-110) in torch CPU ops.  tests/test_adamw_restatement.py pins it to
+# tests/golden/adamw_trace.npz bit for bit; the GPU tests use it where the trace has no case (chunk boundaries, tails, views).
+# torch's own composite ops (add_ with alpha, addcmul_, addcdiv_) fuse their multiply-add on some CPUs' vector kernels and not on others',
+# so each is written out as the single roundings the trace holds: _fma where it fused (exact product and sum in float64, one rounding to
+# float32 — the float64 sum's own rounding is 2^29 times finer), plain float32 ops elsewhere.
+# The square root goes through float64 as well: torch's float32 sqrt is the correctly rounded one on some hosts and up to an ulp off on
+# others (an EPYC 9575F differed from the trace in a sixth of the elements); the float64 root rounded to float32 is correct on all.
+def _fma(a, b, c):
+    return (a.double() * b.double() + c.double()).float()
+
+
+def clip_adamw_step(params, grads, state, lr, weight_decay, betas=(0.9, 0.98), eps=1e-6, max_norm=5.0, norm=None):
+    """One update, in place.  params: {name: float32 CPU tensor}; grads: {name: gradient} for the tensors that got one (the others are
+    skipped: no moment update, no decay, their step count stays); state: {name: {'step', 'exp_avg', 'exp_avg_sq'}}, filled on first use;
+    lr: this step's learning rate; weight_decay: {name: value}; norm: the total gradient norm as a float32 value if the caller has it
+    (the order of a float32 sum of squares is torch's business and differs between CPUs), else computed here as clip_grad_norm_ does.
+    -> the total gradient norm before clipping."""
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32)
+    grads = {n: grads[n] for n in params if n in grads}
+    if norm is None:
+        norm = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g) for g in grads.values()]))
+    norm = torch.as_tensor(norm, dtype=torch.float32)
+    coef = torch.clamp(max_norm / (norm + 1e-6), max=1.0)                    # clamp(max_norm / (norm + 1e-6), max = 1), multiplied in always
+    b1, b2 = betas
+    for n, g in grads.items():
+        g = g * coef
+        p = params[n]
+        st = state.setdefault(n, {'step': 0, 'exp_avg': torch.zeros_like(p), 'exp_avg_sq': torch.zeros_like(p)})
+        st['step'] += 1                                       # the parameter's own count: a skipped step makes its bias correction lag
+        m, v, t = st['exp_avg'], st['exp_avg_sq'], st['step']
+        m.copy_(_fma(g, f32(1.0 - b1), m * f32(b1)))                         # exp_avg.mul_(beta1).add_(grad, alpha = 1 - beta1)
+        v.copy_(_fma(g * f32(1.0 - b2), g, v * f32(b2)))                     # exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+        denom = v.double().sqrt().float() + f32(eps)                         # exp_avg_sq.sqrt().add_(eps)
+        step_size = lr * math.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)
+        p.copy_(p + (f32(-step_size) * m) / denom)                           # p.addcdiv_(exp_avg, denom, value = -step_size)
+        if weight_decay[n] > 0.0:
+            p.copy_(_fma(f32(-lr * weight_decay[n]), p, p))                  # p.add_(p, alpha = -lr * weight_decay): decoupled, after the update
+    return float(norm)
 
 
 # ---- host restatement of the attention dropout mask ------------------------------------------------------------------------------

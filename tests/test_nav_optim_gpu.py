@@ -22,8 +22,9 @@ SMALL = [n for n, _ in SHAPES if n not in ('chunk', 'odd', 'mat')]
 UNCOVERED = ('frozen', 'unused')
 
 
-def _case(names=None, copies=True, seed=0):
-    """parameters on the device, the hand-made 'nav' arena, and the cached operand copies the forward passes would have made"""
+def _case(names=None, copies=True, seed=0, tasks=('nav',), tasks_of=None):
+    """parameters on the device, the hand-made arena (every tensor but `unused` used by `tasks`, or by tasks_of[name]), and the cached
+    operand copies the forward passes would have made"""
     from vln_goat_amd import dp, hipops
     gen = torch.Generator().manual_seed(seed)
     params, base = {}, None
@@ -38,7 +39,7 @@ def _case(names=None, copies=True, seed=0):
             assert params[n].data_ptr() % 16 == 4
         else:
             params[n] = torch.nn.Parameter(w.cuda(), requires_grad=n != 'frozen')
-    usage = {id(p): (set() if n == 'unused' else {'nav'}) for n, p in params.items()}
+    usage = {id(p): (set() if n == 'unused' else set((tasks_of or {}).get(n, tasks))) for n, p in params.items()}
     arena = dp.GradArena(list(params.values()), usage).attach()
     assert all(id(params[n]) not in arena.views for n in UNCOVERED if n in params)
     bf = torch.bfloat16
@@ -260,6 +261,51 @@ def test_state_interchanges_with_torch_on_the_device(algo):
     assert opt.steps_done() == 3
     _check_params(params, cpu, (algo, 'torch->fused'))
     _check_moments(opt, topt, params, cpu, algo, (algo, 'torch->fused'))
+
+
+def test_fused_adamw_three_steps_on_the_edge_shapes():
+    """The pre-training update (optim.FusedAdamW: goat_grad_sqnorm + goat_adamw_step) on the shapes above, which its own trace test
+    (test_train_step_gpu.py, largest tensor 300x64, everything aligned and below one chunk) never reaches: chunk boundaries, the odd tail, the
+    shifted view, the K-padded and the concatenated copies.  Two task keys; `s3` belongs to 'a' only, so its step count and bias correction
+    lag.  Step 0 is clipped (norm > 5), steps 1-2 are not, the learning rate changes before step 2; `bias` is in the no-decay group.
+    Against helpers.clip_adamw_step (pinned bit for bit to the reference's trace by test_adamw_restatement.py), bounds of the trace test."""
+    from helpers import clip_adamw_step
+    from vln_goat_amd import optim
+    params, arena = _case(tasks=('a', 'b'), tasks_of={'s3': ('a',)})
+    start = {n: params[n].detach().clone() for n in UNCOVERED}
+    cpu = {n: p.detach().cpu().clone() for n, p in params.items() if n not in UNCOVERED}
+    wd = {n: 0.0 if any(nd in n for nd in optim.NO_DECAY) else 0.01 for n in cpu}
+    state = {}
+    opt = optim.FusedAdamW(params.items(), arena, lr=1e-3, betas=(0.9, 0.98), weight_decay=0.01)
+    assert opt.param_groups[1]['names'] == ['bias'] and len(opt.param_groups[0]['names']) == len(SHAPES) - 3
+    for step, (task, scale, lr) in enumerate((('a', 0.1, 1e-3), ('b', 0.00625, 1e-3), ('a', 0.005, 4e-4))):
+        grads = _grads(params, 400 + step, scale)
+        if task == 'b':
+            del grads['s3']
+        ref_norm = clip_adamw_step(cpu, grads, state, lr, wd, betas=(0.9, 0.98), eps=1e-6, max_norm=5.0)
+        assert (ref_norm > 5.0) == (step == 0), (step, ref_norm)
+        arena.bind(task)
+        arena.flat.zero_()
+        _load(arena, params, grads)
+        for g in opt.param_groups:
+            g['lr'] = lr
+        opt.step(task, max_norm=5.0)
+        torch.cuda.synchronize()
+        norm = opt.last_grad_norm()
+        print('adamw step %d (%s): norm %.6f (restatement %.6f)' % (step, task, norm, ref_norm))
+        assert abs(norm - ref_norm) <= 1e-4 * ref_norm, (step, norm, ref_norm)
+        for n, ref in cpu.items():
+            err = float((params[n].detach().cpu() - ref).abs().max())
+            print('  %-8s |p - ref| %.3e' % (n, err))
+            assert err <= 2e-6 * max(1.0, float(ref.abs().max())) + 1e-9, (step, n, err)
+            st = opt.state_of(params[n])
+            if n in state:
+                for k in MOMENTS['adamW']:
+                    _close(st[k].detach().cpu(), state[n][k], *M_TOL[k], (step, n, k))
+        _check_copies(params)
+        for n in UNCOVERED:
+            assert torch.equal(params[n].detach(), start[n]), n
+    assert opt.steps[id(params['s3'])] == 2 == state['s3']['step'] and all(opt.steps[id(params[n])] == 3 for n in cpu if n != 's3')
 
 
 def _to_device(ep):

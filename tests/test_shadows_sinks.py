@@ -29,7 +29,7 @@ def _accessors(q, k, v, bq, bk):
 
 
 def test_shadow_keys_are_the_documented_tuples():
-    """optim.FusedAdamW._copies and tests/test_train_step_gpu.py read these tuples: they are the literal ones of shadows.py's table"""
+    """optim._copies and tests/test_train_step_gpu.py read these tuples: they are the literal ones of shadows.py's table"""
     q, k, v, bq, bk = _params()
     want = {}
     for owner, call, key, ref in _accessors(q, k, v, bq, bk):
@@ -184,7 +184,7 @@ def test_arena_epoch_is_the_list_first_touch_reads():
 
 
 def test_fused_adamw_copies_reads_the_shadow_keys():
-    """optim.FusedAdamW._copies on cached copies of every kind: which copies the update kernel refreshes itself (their addresses, in
+    """optim._copies on cached copies of every kind: which copies the update kernel refreshes itself (their addresses, in
     the parameters' element order) and which are left to refresh_shadows — the slot rules of the kernel's per-tensor record (two bf16
     images or one K-padded + one bf16, one float32 image)."""
     from vln_goat_amd import optim, shadows
@@ -198,7 +198,7 @@ def test_fused_adamw_copies_reads_the_shadow_keys():
     kv, k_plain, k_rows = shadows._shadow_cat((k, v), bf), shadows._shadow(k, bf), shadows._shadow_rows_padded(k, bf, 64)
     biases, b_padded = shadows._cat_bias((bq, bk, bv)), shadows._bias_padded(bq, 64)
     padded = shadows._shadow(w7, bf, False, 1)
-    slots, done = optim.FusedAdamW._copies(None, [q, k, v, bq, bk, bv, w7])
+    slots, done = optim._copies([q, k, v, bq, bk, bv, w7])
     # k: the kv image takes its first slot, the plain one its second (cache order: k's own entries, after q's qkv image was weighed
     # and refused for want of a third slot on k) — whatever the order, every copy in `done` is completely covered by slots
     assert plain.data_ptr() in done and padded.data_ptr() in done and biases.data_ptr() in done

@@ -32,139 +32,14 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* __restrict__ a
   if (threadIdx.x == 0) atomicAdd(out_sq, part[0] + part[1] + part[2] + part[3]);
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(const float* __restrict__ grad, float* __restrict__ m_, float* __restrict__ v_,
-                                                    const goat_adamw_tensor* __restrict__ tensors, const int32_t* __restrict__ chunks,
-                                                    float beta1, float beta2, float eps, float max_norm, const float* __restrict__ sq_norm) {
-  const int ti = chunks[2 * blockIdx.x], first = chunks[2 * blockIdx.x + 1];
-  const goat_adamw_tensor t = tensors[ti];
-  float clip = 1.f;
-  if (max_norm > 0.f && sq_norm != nullptr) {
-    const float c = max_norm / (sqrtf(*sq_norm) + 1e-6f);        // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1)
-    clip = c < 1.f ? c : 1.f;
-  }
-  const int64_t n = t.numel;
-  const int64_t end = (int64_t)first + CHUNK < n ? (int64_t)first + CHUNK : n;
-  const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
-  bf16_t* s0 = reinterpret_cast<bf16_t*>(t.shadow0);
-  bf16_t* s1 = reinterpret_cast<bf16_t*>(t.shadow1);
-  float* sf = t.shadow_f32;
-  const bool padded = t.cols > 0;            // shadow0 = row-padded image (leading dimension ld0): scalar stores, tiny tensors
-  const bool vec = !padded && (sf == nullptr || (reinterpret_cast<uintptr_t>(sf) & 15) == 0) && ((t.arena_off & 3) == 0) && ((reinterpret_cast<uintptr_t>(t.param) & 15) == 0) &&
-                   (s0 == nullptr || (reinterpret_cast<uintptr_t>(s0) & 7) == 0) && (s1 == nullptr || (reinterpret_cast<uintptr_t>(s1) & 7) == 0);
-  for (int64_t i = first + threadIdx.x * 4; i < end; i += 256 * 4) {
-    float g[4], m[4], v[4], p[4];
-    const int cnt = (int)((end - i) < 4 ? (end - i) : 4);
-    const bool full = vec && cnt == 4 && ((i & 3) == 0);
-    if (full) {
-      const f32x4 g4 = *reinterpret_cast<const f32x4*>(grad + t.arena_off + i), m4 = *reinterpret_cast<const f32x4*>(m_ + t.arena_off + i),
-                  v4 = *reinterpret_cast<const f32x4*>(v_ + t.arena_off + i), p4 = *reinterpret_cast<const f32x4*>(t.param + i);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { g[k] = g4[k]; m[k] = m4[k]; v[k] = v4[k]; p[k] = p4[k]; }
-    } else {
-      for (int k = 0; k < cnt; ++k) { g[k] = grad[t.arena_off + i + k]; m[k] = m_[t.arena_off + i + k]; v[k] = v_[t.arena_off + i + k]; p[k] = t.param[i + k]; }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k < cnt) {
-        const float gc = g[k] * clip;
-        m[k] = m[k] * beta1 + omb1 * gc;                         // exp_avg.mul_(beta1).add_(grad, alpha = 1 - beta1)
-        v[k] = v[k] * beta2 + omb2 * (gc * gc);                  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-        const float denom = sqrtf(v[k]) + eps;
-        p[k] = p[k] - t.step_size * (m[k] / denom);             // p.addcdiv_(exp_avg, denom, value = -step_size)
-        if (t.decay > 0.f) p[k] = p[k] - t.decay * p[k];         // p.add_(p, alpha = -lr * weight_decay)   (after the update)
-      }
-    }
-    if (full) {
-      f32x4 m4, v4, p4;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { m4[k] = m[k]; v4[k] = v[k]; p4[k] = p[k]; }
-      *reinterpret_cast<f32x4*>(m_ + t.arena_off + i) = m4;
-      *reinterpret_cast<f32x4*>(v_ + t.arena_off + i) = v4;
-      *reinterpret_cast<f32x4*>(t.param + i) = p4;
-      bf16x4 b;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) b[k] = (bf16_t)p[k];
-      if (s0) *reinterpret_cast<bf16x4*>(s0 + i) = b;
-      if (s1) *reinterpret_cast<bf16x4*>(s1 + i) = b;
-      if (sf) *reinterpret_cast<f32x4*>(sf + i) = p4;
-    } else {
-      for (int k = 0; k < cnt; ++k) {
-        m_[t.arena_off + i + k] = m[k]; v_[t.arena_off + i + k] = v[k]; t.param[i + k] = p[k];
-        if (s0) s0[padded ? ((i + k) / t.cols) * (int64_t)t.ld0 + (i + k) % t.cols : i + k] = (bf16_t)p[k];
-        if (s1) s1[i + k] = (bf16_t)p[k];
-        if (sf) sf[i + k] = p[k];
-      }
-    }
-  }
-}
-
-// What goat_optim_step needs per launch, formed ONCE per thread from the device-resident hyper-parameter block, step counter and squared
-// norm.  The double expressions are the ones torch forms on the host (torch/optim/{adamw,adam,rmsprop,sgd}.py, single-tensor path) and
-// are rounded to float where torch hands them to a float32 tensor op.
-struct OptimScalars {
-  float clip, decay_mul, wd, b1, omb1, b2, omb2, eps, neg_step, bc2_sqrt;
-};
-
-template <int ALGO>
-__device__ __forceinline__ OptimScalars optim_scalars(const goat_optim_hyper* __restrict__ h, const int64_t* __restrict__ step,
-                                                      const float* __restrict__ sq_norm) {
-  OptimScalars s;
-  const double lr = h->lr, b1 = h->beta1, b2 = h->beta2, wd = h->weight_decay, max_norm = h->max_norm;
-  s.clip = 1.f;
-  if (max_norm > 0.0) {
-    const float c = (float)max_norm / (sqrtf(*sq_norm) + 1e-6f);        // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1)
-    s.clip = c < 1.f ? c : 1.f;
-  }
-  s.decay_mul = (float)(1.0 - lr * wd);                                 // AdamW: param.mul_(1 - lr * weight_decay)
-  s.wd = (float)wd;
-  s.b1 = (float)b1;
-  s.omb1 = (float)(1.0 - b1);
-  s.b2 = (float)b2;
-  s.omb2 = (float)(1.0 - b2);
-  s.eps = (float)h->eps;
-  s.neg_step = (float)(-lr);
-  s.bc2_sqrt = 1.f;
-  if (ALGO == GOAT_OPT_ADAMW || ALGO == GOAT_OPT_ADAM) {
-    const double t = (double)(*step + 1);                               // the counter holds the COMPLETED steps
-    const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
-    s.neg_step = (float)(-(lr / bc1));                                  // step_size = lr / bias_correction1
-    s.bc2_sqrt = (float)sqrt(bc2);                                      // bias_correction2 ** 0.5
-  }
-  return s;
-}
-
-// one element; g arrives unclipped.  ALGO is a template argument: each instantiation holds one algorithm's arithmetic.
-template <int ALGO>
-__device__ __forceinline__ void optim_update(float g, float& m, float& v, float& p, const OptimScalars& s) {
-  g *= s.clip;                                                          // clip_grad_norm_ multiplies always (by 1.0 when not clipping)
-  if (ALGO == GOAT_OPT_ADAMW) p *= s.decay_mul;
-  else if (s.wd != 0.f) g += s.wd * p;                                  // grad.add(param, alpha = weight_decay)
-  if (ALGO == GOAT_OPT_ADAMW || ALGO == GOAT_OPT_ADAM) {
-    m = s.omb1 < 0.5f ? m + s.omb1 * (g - m) : g - (g - m) * (1.f - s.omb1);   // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * s.b2 + (s.omb2 * g) * g;                                    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-    const float denom = sqrtf(v) / s.bc2_sqrt + s.eps;                  // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-    p = p + (s.neg_step * m) / denom;                                   // param.addcdiv_(exp_avg, denom, value = -step_size)
-  } else if (ALGO == GOAT_OPT_RMSPROP) {
-    v = v * s.b1 + (s.omb1 * g) * g;                                    // square_avg.mul_(alpha).addcmul_(grad, grad, value = 1 - alpha)
-    p = p + (s.neg_step * g) / (sqrtf(v) + s.eps);                      // param.addcdiv_(grad, square_avg.sqrt().add_(eps), value = -lr)
-  } else {
-    p = p + s.neg_step * g;                                             // param.add_(grad, alpha = -lr)
-  }
-}
-
-// Same chunk table, vector / scalar split and shadow slots as adamw_kernel.  m_ is read and written by AdamW / Adam only, v_ by all but SGD
-// (it is RMSprop's square_avg).
-template <int ALGO>
-__global__ __launch_bounds__(256) void optim_kernel(const float* __restrict__ grad, float* __restrict__ m_, float* __restrict__ v_,
-                                                    const goat_optim_tensor* __restrict__ tensors, const int32_t* __restrict__ chunks,
-                                                    const goat_optim_hyper* __restrict__ hyper, const int64_t* __restrict__ step,
-                                                    const float* __restrict__ sq_norm) {
-  constexpr bool HAS_M = ALGO == GOAT_OPT_ADAMW || ALGO == GOAT_OPT_ADAM, HAS_V = ALGO != GOAT_OPT_SGD;
-  const int ti = chunks[2 * blockIdx.x], first = chunks[2 * blockIdx.x + 1];
-  const goat_optim_tensor t = tensors[ti];
+// One chunk of one tensor, for every update below: the guard, the vector / scalar split, 16-byte loads, `update(g, m, v, p)` on up to four
+// elements, 16-byte stores, the three shadow slots and the row-padded store.  Tensor is goat_adamw_tensor or goat_optim_tensor (the members
+// used here have the same names in both); m_ is touched only if HAS_M, v_ only if HAS_V.
+template <bool HAS_M, bool HAS_V, typename Tensor, typename Update>
+__device__ __forceinline__ void walk_chunk(const Tensor& t, int first, const float* __restrict__ grad, float* __restrict__ m_,
+                                           float* __restrict__ v_, Update update) {
   const int64_t n = t.numel;
   if (first < 0 || first >= n) return;
-  const OptimScalars s = optim_scalars<ALGO>(hyper, step, sq_norm);
   const int64_t end = (int64_t)first + CHUNK < n ? (int64_t)first + CHUNK : n;
   const float* gp = grad + t.arena_off;
   float* mp = HAS_M ? m_ + t.arena_off : nullptr;
@@ -195,7 +70,7 @@ __global__ __launch_bounds__(256) void optim_kernel(const float* __restrict__ gr
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (k < cnt) optim_update<ALGO>(g[k], m[k], v[k], p[k], s);
+      if (k < cnt) update(g[k], m[k], v[k], p[k]);
     if (full) {
       f32x4 m4, v4, p4;
 #pragma unroll
@@ -220,6 +95,103 @@ __global__ __launch_bounds__(256) void optim_kernel(const float* __restrict__ gr
       }
     }
   }
+}
+
+// The update arithmetic below is compiled with contraction off and names its fused multiply-adds itself (__builtin_fmaf): every product and
+// sum rounds where the source says, whatever code surrounds it.  sqrtf and the divisions are the correctly rounded ones.
+
+__global__ __launch_bounds__(256) void adamw_kernel(const float* __restrict__ grad, float* __restrict__ m_, float* __restrict__ v_,
+                                                    const goat_adamw_tensor* __restrict__ tensors, const int32_t* __restrict__ chunks,
+                                                    float beta1, float beta2, float eps, float max_norm, const float* __restrict__ sq_norm) {
+  const goat_adamw_tensor t = tensors[chunks[2 * blockIdx.x]];
+  float clip = 1.f;
+  if (max_norm > 0.f && sq_norm != nullptr) {
+    const float c = max_norm / (sqrtf(*sq_norm) + 1e-6f);        // torch.nn.utils.clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1)
+    clip = c < 1.f ? c : 1.f;
+  }
+  const float omb1 = 1.f - beta1, omb2 = 1.f - beta2;
+  walk_chunk<true, true>(t, chunks[2 * blockIdx.x + 1], grad, m_, v_, [&](float g, float& m, float& v, float& p) {
+#pragma clang fp contract(off)
+    const float gc = g * clip;
+    m = m * beta1 + omb1 * gc;                                   // exp_avg.mul_(beta1).add_(grad, alpha = 1 - beta1)
+    v = v * beta2 + omb2 * (gc * gc);                            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+    const float denom = sqrtf(v) + eps;
+    p = __builtin_fmaf(-t.step_size, m / denom, p);              // p.addcdiv_(exp_avg, denom, value = -step_size)
+    if (t.decay > 0.f) p = __builtin_fmaf(-t.decay, p, p);       // p.add_(p, alpha = -lr * weight_decay)   (after the update)
+  });
+}
+
+// What goat_optim_step needs per launch, formed ONCE per thread from the device-resident hyper-parameter block, step counter and squared
+// norm.  The double expressions are the ones torch forms on the host (torch/optim/{adamw,adam,rmsprop,sgd}.py, single-tensor path) and
+// are rounded to float where torch hands them to a float32 tensor op.
+struct OptimScalars {
+  float clip, decay_mul, wd, b1, omb1, b2, omb2, eps, neg_step, bc2_sqrt;
+};
+
+template <int ALGO>
+__device__ __forceinline__ OptimScalars optim_scalars(const goat_optim_hyper* __restrict__ h, const int64_t* __restrict__ step,
+                                                      const float* __restrict__ sq_norm) {
+#pragma clang fp contract(off)
+  OptimScalars s;
+  const double lr = h->lr, b1 = h->beta1, b2 = h->beta2, wd = h->weight_decay, max_norm = h->max_norm;
+  s.clip = 1.f;
+  if (max_norm > 0.0) {
+    const float c = (float)max_norm / (sqrtf(*sq_norm) + 1e-6f);        // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max = 1)
+    s.clip = c < 1.f ? c : 1.f;
+  }
+  s.decay_mul = (float)__builtin_fma(-lr, wd, 1.0);                     // AdamW: param.mul_(1 - lr * weight_decay)
+  s.wd = (float)wd;
+  s.b1 = (float)b1;
+  s.omb1 = (float)(1.0 - b1);
+  s.b2 = (float)b2;
+  s.omb2 = (float)(1.0 - b2);
+  s.eps = (float)h->eps;
+  s.neg_step = (float)(-lr);
+  s.bc2_sqrt = 1.f;
+  if (ALGO == GOAT_OPT_ADAMW || ALGO == GOAT_OPT_ADAM) {
+    const double t = (double)(*step + 1);                               // the counter holds the COMPLETED steps
+    const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+    s.neg_step = (float)(-(lr / bc1));                                  // step_size = lr / bias_correction1
+    s.bc2_sqrt = (float)sqrt(bc2);                                      // bias_correction2 ** 0.5
+  }
+  return s;
+}
+
+// one element; g_raw is the unclipped gradient.  ALGO is a template argument: each instantiation holds one algorithm's arithmetic.
+template <int ALGO>
+__device__ __forceinline__ void optim_update(float g_raw, float& m, float& v, float& p, const OptimScalars& s) {
+#pragma clang fp contract(off)
+  float g = g_raw * s.clip;                                             // clip_grad_norm_ multiplies always (by 1.0 when not clipping)
+  if (ALGO == GOAT_OPT_ADAMW) p *= s.decay_mul;
+  else if (s.wd != 0.f) g = g + s.wd * p;                               // grad.add(param, alpha = weight_decay)
+  if (ALGO == GOAT_OPT_ADAMW || ALGO == GOAT_OPT_ADAM) {
+    // Which product of a sum rides in the fma is kept as these kernels were first compiled (profiles/optim_fold_isa_diff.txt), hence the
+    // two forms per line: AdamW takes grad - exp_avg from the unrounded clip * grad and fuses beta2 * v, Adam fuses the other product.
+    const float d = ALGO == GOAT_OPT_ADAMW ? __builtin_fmaf(s.clip, g_raw, -m) : g - m;
+    m = s.omb1 < 0.5f ? __builtin_fmaf(s.omb1, d, m) : __builtin_fmaf(-(1.f - s.omb1), d, g);                  // exp_avg.lerp_(grad, 1 - beta1)
+    // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+    v = ALGO == GOAT_OPT_ADAMW ? __builtin_fmaf(v, s.b2, (s.omb2 * g) * g) : __builtin_fmaf(s.omb2 * g, g, v * s.b2);
+    const float denom = sqrtf(v) / s.bc2_sqrt + s.eps;                  // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+    p = p + (s.neg_step * m) / denom;                                   // param.addcdiv_(exp_avg, denom, value = -step_size)
+  } else if (ALGO == GOAT_OPT_RMSPROP) {
+    v = __builtin_fmaf(s.omb1 * g, g, v * s.b1);                        // square_avg.mul_(alpha).addcmul_(grad, grad, value = 1 - alpha)
+    p = p + (s.neg_step * g) / (sqrtf(v) + s.eps);                      // param.addcdiv_(grad, square_avg.sqrt().add_(eps), value = -lr)
+  } else {
+    p = __builtin_fmaf(s.neg_step, g, p);                               // param.add_(grad, alpha = -lr)
+  }
+}
+
+// m_ is read and written by AdamW / Adam only, v_ by all but SGD (it is RMSprop's square_avg).
+template <int ALGO>
+__global__ __launch_bounds__(256) void optim_kernel(const float* __restrict__ grad, float* __restrict__ m_, float* __restrict__ v_,
+                                                    const goat_optim_tensor* __restrict__ tensors, const int32_t* __restrict__ chunks,
+                                                    const goat_optim_hyper* __restrict__ hyper, const int64_t* __restrict__ step,
+                                                    const float* __restrict__ sq_norm) {
+  constexpr bool HAS_M = ALGO == GOAT_OPT_ADAMW || ALGO == GOAT_OPT_ADAM, HAS_V = ALGO != GOAT_OPT_SGD;
+  const goat_optim_tensor t = tensors[chunks[2 * blockIdx.x]];
+  const OptimScalars s = optim_scalars<ALGO>(hyper, step, sq_norm);
+  walk_chunk<HAS_M, HAS_V>(t, chunks[2 * blockIdx.x + 1], grad, m_, v_,
+                           [&](float g, float& m, float& v, float& p) { optim_update<ALGO>(g, m, v, p, s); });
 }
 
 // the step's own stream-ordered tail: the counter moves on, the squared norm is kept for last_grad_norm() and cleared for the next

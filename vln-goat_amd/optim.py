@@ -96,6 +96,76 @@ def _copies(plist):
     return slots, done
 
 
+def _task_key(task):
+    return task.split('_')[0] if task is not None else None
+
+
+class _Upload:
+    """A block of device memory written from the host: staged through pinned memory and copied asynchronously on the current stream, so
+    work launched after send() reads the new bytes and work launched before it the old ones.  The event orders the NEXT send() behind this
+    copy's read of the pinned block (graph-replay loops never synchronise).  A CPU arena has no pinned memory: a plain copy."""
+
+    def __init__(self, nbytes, dev):
+        self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self._pinned = torch.zeros(nbytes, dtype=torch.uint8).pin_memory() if dev.type == 'cuda' else None
+        self._copied = None
+
+    def send(self, raw):
+        if self._pinned is None:
+            self.dev.copy_(raw)
+            return
+        if self._copied is not None:
+            self._copied.synchronize()
+        self._pinned.copy_(raw)
+        self.dev.copy_(self._pinned, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record()
+
+
+class _Table:
+    """What either update hands its kernels for the parameters among `ids` that the task `key` uses (every arena parameter of `ids` if
+    None), in arena order: the chunk table, the arena ranges of the norm and the tensor table (`struct`: _lib.AdamwTensor or
+    _lib.OptimTensor, which name the shared fields alike)."""
+
+    def __init__(self, arena, ids, key, struct):
+        self.arena = arena
+        self.params = [p for p in arena.params if id(p) in ids and (arena.tasks_of[id(p)] is None or key is None or key in arena.tasks_of[id(p)])]
+        chunks, rng = [], []
+        for i, p in enumerate(self.params):
+            for first in range(0, p.numel(), CHUNK):
+                chunks += [i, first]
+            a = arena.offsets[id(p)]
+            rng += [a, a + p.numel()]        # the norm runs over the parameters' own elements (the alignment padding between arena slices is never written: zeros)
+        dev = arena.flat.device
+        self.chunks, self.nchunks = torch.tensor(chunks, dtype=torch.int32, device=dev), len(chunks) // 2
+        self.ranges, self.n_ranges = torch.tensor(rng, dtype=torch.int64, device=dev), len(rng) // 2
+        self.host = (struct * max(1, len(self.params)))()
+        self.entries = list(self.host)[:len(self.params)]       # (views into `host`, made once: indexing a ctypes array builds a new object)
+        self._upload = _Upload(ctypes.sizeof(self.host), dev)
+        self.dev = self._upload.dev
+
+    def fill(self):
+        """the eight shared fields of every entry from the cached copies of now -> `done` of _copies()"""
+        slots, done = _copies(self.params)
+        for e, p in zip(self.entries, self.params):
+            sl = slots[id(p)]
+            e.param, e.arena_off, e.numel = p.data_ptr(), self.arena.offsets[id(p)], p.numel()
+            bf = list(sl['bf16'])
+            if sl['pad'] is not None:
+                e.shadow0, e.cols, e.ld0 = sl['pad']
+                e.shadow1 = bf[0] if bf else None
+            else:
+                e.cols, e.ld0 = 0, 0
+                e.shadow0 = bf[0] if len(bf) > 0 else None
+                e.shadow1 = bf[1] if len(bf) > 1 else None
+            e.shadow_f32 = sl['f32']
+        return done
+
+    def send(self):
+        nbytes = ctypes.sizeof(self.host)
+        self._upload.send(torch.frombuffer((ctypes.c_uint8 * nbytes).from_address(ctypes.addressof(self.host)), dtype=torch.uint8))
+
+
 class FusedAdamW:
     """optimizer over the parameters of a dp.GradArena.
 
@@ -124,87 +194,38 @@ class FusedAdamW:
         self.exp_avg_sq = torch.zeros_like(arena.flat)
         self.steps = {id(p): 0 for _, p in named}                                   # state['step'] of every parameter
         self._sq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self._plans = {}
+        self._tables = {}                # per task key (static): which tensors, their chunks, the arena ranges of the norm
         self._by_id = {id(p): p for _, p in named}
         self.last_refreshed = 0          # copies rebuilt by torch ops after the last step (0 in the steady bf16 state)
-
-    # -- per-task plan (static): which tensors, their chunks, the arena ranges of the norm --------------------------------------
-    def _plan(self, task):
-        key = task.split('_')[0] if task is not None else None
-        pl = self._plans.get(key)
-        if pl is not None:
-            return pl
-        arena = self.arena
-        plist = [p for p in arena.params if id(p) in self.names and (arena.tasks_of[id(p)] is None or key is None or key in arena.tasks_of[id(p)])]
-        chunks = []
-        for i, p in enumerate(plist):
-            for first in range(0, p.numel(), CHUNK):
-                chunks += [i, first]
-        dev = arena.flat.device
-        # the norm runs over the parameters' own elements (the alignment padding between arena slices is never written: zeros)
-        rng = []
-        for p in plist:
-            a = arena.offsets[id(p)]
-            rng += [a, a + p.numel()]
-        nbytes = max(1, len(plist)) * ctypes.sizeof(_lib.AdamwTensor)
-        pl = {'params': plist, 'chunks': torch.tensor(chunks, dtype=torch.int32, device=dev), 'nchunks': len(chunks) // 2,
-              'ranges': torch.tensor(rng, dtype=torch.int64, device=dev), 'n_ranges': len(rng) // 2,
-              'host': (_lib.AdamwTensor * max(1, len(plist)))(), 'dev': torch.empty(nbytes, dtype=torch.uint8, device=dev),
-              'pinned': torch.empty(nbytes, dtype=torch.uint8).pin_memory() if dev.type == 'cuda' else None}
-        self._plans[key] = pl
-        return pl
-
-    def _copies(self, plist):
-        return _copies(plist)
 
     def step(self, task=None, max_norm=5.0):
         """clip_grad_norm_(max_norm) + AdamW on the parameters `task` uses (all arena parameters if None)."""
         from . import hipops
-        pl = self._plan(task)
-        if not pl['params']:
+        key = _task_key(task)
+        tb = self._tables.get(key)
+        if tb is None:
+            tb = self._tables[key] = _Table(self.arena, self.names, key, _lib.AdamwTensor)
+        if not tb.params:
             return
         arena = self.arena
         b1, b2 = self.betas
-        slots, done = self._copies(pl['params'])
-        host = pl['host']
-        for i, p in enumerate(pl['params']):
+        done = tb.fill()
+        for e, p in zip(tb.entries, tb.params):
             self.steps[id(p)] += 1
             t = self.steps[id(p)]
             g = self.param_groups[self._group_of[self.names[id(p)]]]
             lr = g['lr']
-            step_size = lr * ((1.0 - b2 ** t) ** 0.5) / (1.0 - b1 ** t) if self.correct_bias else lr
-            sl = slots[id(p)]
-            e = host[i]
-            e.param, e.arena_off, e.numel = p.data_ptr(), arena.offsets[id(p)], p.numel()
-            bf = list(sl['bf16'])
-            if sl['pad'] is not None:
-                e.shadow0, e.cols, e.ld0 = sl['pad']
-                e.shadow1 = bf[0] if bf else None
-            else:
-                e.cols, e.ld0 = 0, 0
-                e.shadow0 = bf[0] if len(bf) > 0 else None
-                e.shadow1 = bf[1] if len(bf) > 1 else None
-            e.shadow_f32 = sl['f32']
-            e.step_size, e.decay = step_size, lr * g['weight_decay']
-        nbytes = ctypes.sizeof(host)
-        raw = torch.frombuffer((ctypes.c_uint8 * nbytes).from_address(ctypes.addressof(host)), dtype=torch.uint8)
-        if pl['pinned'] is not None:
-            if pl.get('copied') is not None:
-                pl['copied'].synchronize()       # the previous step's H2D copy has read the pinned table (graph-replay loops never sync)
-            pl['pinned'].copy_(raw)
-            pl['dev'].copy_(pl['pinned'], non_blocking=True)
-            pl['copied'] = torch.cuda.Event()
-            pl['copied'].record()
-        else:
-            pl['dev'].copy_(raw)
+            e.step_size = lr * ((1.0 - b2 ** t) ** 0.5) / (1.0 - b1 ** t) if self.correct_bias else lr
+            e.decay = lr * g['weight_decay']
+        tb.send()
         self._sq.zero_()
         clip = max_norm is not None and max_norm > 0
-        launch('goat_grad_sqnorm', arena.flat, pl['ranges'], pl['n_ranges'], self._sq)
-        launch('goat_adamw_step', arena.flat, self.exp_avg, self.exp_avg_sq, pl['dev'], pl['chunks'], pl['nchunks'], b1, b2, self.eps,
+        launch('goat_grad_sqnorm', arena.flat, tb.ranges, tb.n_ranges, self._sq)
+        launch('goat_adamw_step', arena.flat, self.exp_avg, self.exp_avg_sq, tb.dev, tb.chunks, tb.nchunks, b1, b2, self.eps,
                float(max_norm) if clip else 0.0, self._sq)
         # the copies the kernel did not cover (transposed / float32 images of the parity mode, a third bf16 copy): same storage, new values
         by_id = self._by_id
-        self.last_refreshed = sum(hipops.refresh_shadows(p, by_id, done) for p in pl['params'])
+        self.last_refreshed = sum(hipops.refresh_shadows(p, by_id, done) for p in tb.params)
 
     def last_grad_norm(self):
         """total gradient norm of the last step() (synchronises)."""
@@ -260,11 +281,10 @@ class FusedTorchOptim:
         self.arena, self.task = arena, task
         named = list(named_params)
         self.all_params = [p for _, p in named]                     # the order state_dict() indexes by
-        key = task.split('_')[0] if task is not None else None
-        covered = {id(p) for _, p in named if id(p) in arena.views and (arena.tasks_of[id(p)] is None or key is None or key in arena.tasks_of[id(p)])}
-        self.params = [p for p in arena.params if id(p) in covered]             # arena order: the kernel's tensor table
-        self.names = {id(p): n for n, p in named if id(p) in covered}
+        self._tb = _Table(arena, {id(p) for _, p in named}, _task_key(task), _lib.OptimTensor)
+        self.params = self._tb.params                                           # arena order: the kernel's tensor table
         self._by_id = {id(p): p for p in self.params}
+        self.names = {id(p): n for n, p in named if id(p) in self._by_id}
         group['params'] = self.all_params
         self.param_groups = [group]
         dev = arena.flat.device
@@ -274,24 +294,10 @@ class FusedTorchOptim:
         self.exp_avg_sq = torch.zeros_like(arena.flat) if nm >= 1 else None      # (RMSprop's square_avg)
         self._t = torch.zeros(1, dtype=torch.int64, device=dev)                 # completed steps, shared by every covered parameter
         self._norm = torch.zeros(2, dtype=torch.float32, device=dev)            # [squared norm being accumulated, that of the last step]
-        self._hyper = torch.zeros(6, dtype=torch.float64, device=dev)           # struct goat_optim_hyper
-        self._hyper_pinned = torch.zeros(6, dtype=torch.float64).pin_memory() if self._cuda else None
-        self._hyper_host, self._hyper_copied = None, None
+        self._hyper = _Upload(ctypes.sizeof(_lib.OptimHyper), dev)              # struct goat_optim_hyper: six doubles
+        self._hyper_host = None
         self._max_norm = 40.0
-        chunks, rng = [], []
-        for i, p in enumerate(self.params):
-            for first in range(0, p.numel(), CHUNK):
-                chunks += [i, first]
-            a = arena.offsets[id(p)]
-            rng += [a, a + p.numel()]        # the norm runs over the parameters' own elements (alignment padding is never written)
-        self._chunks = torch.tensor(chunks, dtype=torch.int32, device=dev)
-        self._nchunks = len(chunks) // 2
-        self._ranges = torch.tensor(rng, dtype=torch.int64, device=dev)
-        nbytes = max(1, len(self.params)) * ctypes.sizeof(_lib.OptimTensor)
-        self._table_host = (_lib.OptimTensor * max(1, len(self.params)))()
-        self._table = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self._table_pinned = torch.zeros(nbytes, dtype=torch.uint8).pin_memory() if self._cuda else None
-        self._table_sig, self._table_copied, self._done, self._keep = None, None, set(), []
+        self._table_sig, self._done, self._keep = None, set(), []
         self.last_refreshed = 0
         self._upload_hyper()
         self._build_table()
@@ -315,16 +321,7 @@ class FusedTorchOptim:
         if self._cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError('FusedTorchOptim: hyper-parameters changed inside a hipGraph capture (%r -> %r); call set_lr() / step() with '
                                'these values once before capturing — a captured step reads them from device memory' % (self._hyper_host, vals))
-        new = torch.tensor(vals, dtype=torch.float64)
-        if self._cuda:
-            if self._hyper_copied is not None:
-                self._hyper_copied.synchronize()        # the previous upload has read the pinned block
-            self._hyper_pinned.copy_(new)
-            self._hyper.copy_(self._hyper_pinned, non_blocking=True)
-            self._hyper_copied = torch.cuda.Event()
-            self._hyper_copied.record()
-        else:
-            self._hyper.copy_(new)
+        self._hyper.send(torch.tensor(vals, dtype=torch.float64).view(torch.uint8))
         self._hyper_host = vals
 
     def set_lr(self, lr):
@@ -351,31 +348,8 @@ class FusedTorchOptim:
             return
         if self._cuda and torch.cuda.is_current_stream_capturing():
             return
-        slots, done = _copies(self.params)
-        host, arena = self._table_host, self.arena
-        for i, p in enumerate(self.params):
-            sl, e = slots[id(p)], host[i]
-            e.param, e.arena_off, e.numel = p.data_ptr(), arena.offsets[id(p)], p.numel()
-            bf = list(sl['bf16'])
-            if sl['pad'] is not None:
-                e.shadow0, e.cols, e.ld0 = sl['pad']
-                e.shadow1 = bf[0] if bf else None
-            else:
-                e.cols, e.ld0 = 0, 0
-                e.shadow0 = bf[0] if len(bf) > 0 else None
-                e.shadow1 = bf[1] if len(bf) > 1 else None
-            e.shadow_f32 = sl['f32']
-        nbytes = ctypes.sizeof(host)
-        raw = torch.frombuffer((ctypes.c_uint8 * nbytes).from_address(ctypes.addressof(host)), dtype=torch.uint8)
-        if self._cuda:
-            if self._table_copied is not None:
-                self._table_copied.synchronize()
-            self._table_pinned.copy_(raw)
-            self._table.copy_(self._table_pinned, non_blocking=True)
-            self._table_copied = torch.cuda.Event()
-            self._table_copied.record()
-        else:
-            self._table.copy_(raw)
+        done = self._tb.fill()
+        self._tb.send()
         # the table holds raw addresses: the copies it names stay alive as long as it is in use
         self._keep = [t for p in self.params for _, t in (p.__dict__.get('_goat_shadow') or {}).values()]
         self._table_sig, self._done = sig, done
@@ -388,9 +362,9 @@ class FusedTorchOptim:
         self._max_norm = max_norm
         self._upload_hyper()
         self._build_table()
-        arena = self.arena
-        launch('goat_grad_sqnorm', arena.flat, self._ranges, len(self.params), self._norm)
-        launch('goat_optim_step', self.algo, arena.flat, self.exp_avg, self.exp_avg_sq, self._table, self._chunks, self._nchunks, self._hyper,
+        arena, tb = self.arena, self._tb
+        launch('goat_grad_sqnorm', arena.flat, tb.ranges, tb.n_ranges, self._norm)
+        launch('goat_optim_step', self.algo, arena.flat, self.exp_avg, self.exp_avg_sq, tb.dev, tb.chunks, tb.nchunks, self._hyper.dev,
                self._t, self._norm)
         launch('goat_optim_advance', self._t, self._norm, _ptr(self._norm, 1))
         # the copies the kernel did not cover (transposed / float32 images of the parity mode, a third bf16 copy): same storage, new values

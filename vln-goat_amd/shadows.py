@@ -1,11 +1,11 @@
 """Weight shadows: cached operand copies of the float32 master weights (bf16 casts, K- / row-padded and concatenated images).
 
 A captured hipGraph has their ADDRESSES baked in, so a stale copy is always rebuilt INTO ITS OWN STORAGE, never replaced by a
-new tensor: graphs captured before an optimizer step read the updated weights after it (optim.FusedAdamW refreshes most copies
-inside its update kernel and the rest through `refresh_shadows`).  torch only: nothing here launches a hand-written kernel.
+new tensor: graphs captured before an optimizer step read the updated weights after it (optim.FusedAdamW and optim.FusedTorchOptim refresh most
+copies inside their update kernels and the rest through `refresh_shadows`).  torch only: nothing here launches a hand-written kernel.
 
 The copies of a parameter live in `param.__dict__['_goat_shadow']`: {key: (version, tensor)}.  A key names what the copy holds —
-this table is the contract between the accessors below, `refresh_shadows`, optim.FusedAdamW._copies and the tests:
+this table is the contract between the accessors below, `refresh_shadows`, optim._copies and the tests:
 
     kind      key                                   owner (holds the cache)    contents
     PLAIN     (dtype, transposed, pad_k)            the weight                 cast [, K zero-padded by pad_k] [, transposed]
