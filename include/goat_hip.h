@@ -578,6 +578,31 @@ int goat_add_n(void* stream, int dtype, const void* const* srcs, int n, void* ou
  * (P/train_r2r_goat.py:301-363) over the gradient arena's per-task ranges.  ptrs / nbytes are HOST arrays. */
 int goat_zero_ranges(void* stream, void* const* ptrs, const int64_t* nbytes, int n);
 
+/* ---- validation metrics (csrc/navmetrics.hip) ----------------------------------------------------------------------------
+ * Every per-trajectory score of the reference's `eval_metrics` (M/r2r/env.py:452-490 `_eval_item`, M/r2r/eval_utils.py `cal_dtw` /
+ * `cal_cls`) for N items in one launch, one 64-thread workgroup per item.  out[N, GOAT_NAV_METRICS_COLS] float64, columns:
+ *   0 nav_error   1 oracle_error   2 trajectory_steps   3 trajectory_lengths   4 gt_lengths   5 success   6 oracle_success   7 spl
+ *   8 DTW   9 nDTW   10 SDTW   11 CLS
+ * dist: the shortest-distance tables of n_scans scans, each a packed row-major [n_s, n_s] float64 block at dist + scan_off[s] with
+ * n_s = scan_n[s]; item_scan[N]: the table of every item.  pred / ref: node indices of the flattened predicted path and of the
+ * ground-truth path in CSR form (item i owns pred[pred_start[i] : pred_start[i + 1]], P_i nodes, and likewise R_i nodes of ref).
+ * success = nav_error < margin (strict), spl = success * gt_len / max(traj_len, gt_len, 0.01), nDTW = exp(-DTW / (margin * R)),
+ * SDTW = success * nDTW, CLS as cal_cls (a one-node reference path gives 0 / 0 = NaN, as there).  With goal / goal_start (CSR of
+ * goal nodes per item; both NULL = the rule above) columns 5 and 6 follow M/reverie/env.py:543-549: the last node / any node of the
+ * predicted path is one of the item's goal nodes.  All arithmetic is IEEE float64 without contraction; DTW is computed by
+ * anti-diagonals with the reference's own add per cell (bit-identical to its matrix); columns 3, 4, 7, 9, 10, 11 hold sums whose order
+ * differs from numpy's.  max_ref >= max_i R_i sizes the LDS (three diagonals): 1 <= max_ref <= 2047; P_i is not capped.
+ * PRECONDITION (the entry cannot read device memory): every node index is in [0, n_s) of its item's scan, every goal index too, the
+ * CSR starts are non-decreasing and inside their arrays, P_i >= 1 and 1 <= R_i.  The kernel writes a row of NaN for an item whose
+ * scan id is outside [0, n_scans), whose P_i or R_i is < 1 or whose R_i exceeds max_ref; it cannot check node indices.
+ * GOAT_E_ARG: a null pointer other than stream / goal / goal_start, or exactly one of goal / goal_start given;
+ * GOAT_E_SHAPE: N < 1, n_scans < 1, max_ref < 1 or max_ref > 2047.  Both are returned before any launch. */
+#define GOAT_NAV_METRICS_COLS 12
+int goat_nav_metrics(void* stream, const double* dist, const int64_t* scan_off, const int32_t* scan_n, int n_scans,
+                     const int32_t* item_scan, const int32_t* pred, const int32_t* pred_start, const int32_t* ref,
+                     const int32_t* ref_start, const int32_t* goal, const int32_t* goal_start, int N, int max_ref, double margin,
+                     double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,12 +213,22 @@ def _joined_rows(out, name, T, n):
 class EpisodePlanner:
     """TeacherEpisode.plan one step at a time: build_step() makes the host tables of step t from the navigator's current state,
     advance(actions) moves it (the teacher's actions when `imitation`, else the given ones — a sampled rollout decides them from the
-    step's logits), finish() adds the joint panorama tables and returns the plan dict.  While a planner is alive it owns te.sim."""
+    step's logits), finish() adds the joint panorama tables and returns the plan dict.  While a planner is alive it owns te.sim.
+    feedback='argmax' (with imitation=False): the validation walk of the reference (M/r2r/agent.py:601-672 under feedback = 'argmax', as
+    NavRollout.run does it): action 0 stops, advance() also takes the step's stop scores (and best objects), and a forced end appends the
+    backtrack to the node with the best stop score and sets `pred_objid`; self.traj is then the agent's prediction."""
 
-    def __init__(self, te, episodes, imitation=True):
-        self.te, self.imitation = te, imitation
+    def __init__(self, te, episodes, imitation=True, feedback=None):
+        if feedback not in (None, 'argmax') or (feedback == 'argmax' and imitation):
+            raise ValueError('EpisodePlanner: feedback is None or \'argmax\' (the latter with imitation=False), got %r' % (feedback,))
+        self.te, self.imitation, self.feedback = te, imitation, feedback
         obs, self.gmaps, self.traj, self.store = start_walk(te.sim, episodes)
         self.B = B = len(obs)
+        if feedback == 'argmax':
+            self.just_ended = np.zeros(B, bool)
+            if te.objects is not None:
+                for tr in self.traj:
+                    tr['pred_objid'] = None
         lang = language_inputs(obs)
         if lang['txt_ids'].shape[1] > te.L:
             raise ValueError('instruction of %d tokens exceeds the text bucket %d' % (lang['txt_ids'].shape[1], te.L))
@@ -287,19 +297,33 @@ class EpisodePlanner:
         self.out.update(out)
         return out
 
-    def advance(self, actions=None):
-        """the move of step t: the teacher's (imitation) or `actions` [B] (indices into the step's map nodes, 0 = [stop])."""
+    def advance(self, actions=None, stop_scores=None, best_obj=None):
+        """the move of step t: the teacher's (imitation) or `actions` [B] (indices into the step's map nodes, 0 = [stop]).
+        feedback='argmax': stop_scores [B] (the step's softmax[:, 0]) and, with objects, best_obj [B] (index of the best object of the
+        current viewpoint) are recorded for the live episodes, as NavRollout.run records them."""
         te, t, obs, gmaps, ended, B = self.te, self.t, self.obs, self.gmaps, self.ended, self.B
         gin, target = self._gin, self._target
         if gin is None:
             raise RuntimeError('advance() before build_step()')
         if not self.imitation and actions is None:
             raise ValueError('a planner of a sampled walk needs the actions of every step')
+        argmax = self.feedback == 'argmax'
+        if argmax:
+            if stop_scores is None or (te.objects is not None and best_obj is None):
+                raise ValueError('an argmax walk needs the stop scores (and, with objects, the best objects) of every step')
+            for i, g in enumerate(gmaps):
+                if not ended[i]:
+                    g.node_stop_scores[obs[i]['viewpoint']] = {'stop': float(stop_scores[i])}
+                    if te.objects is not None:
+                        ids = obs[i]['obj_ids']
+                        g.node_stop_scores[obs[i]['viewpoint']]['og'] = ids[int(best_obj[i])] if len(ids) > 0 else None
         moves = []
         for i in range(B):
-            stop = obs[i]['viewpoint'] == obs[i]['gt_path'][-1]
+            stop = (int(actions[i]) == 0) if argmax else (obs[i]['viewpoint'] == obs[i]['gt_path'][-1])
             if stop or ended[i] or gin['no_vp_left'][i] or t == te.T - 1:
                 moves.append(None)
+                if argmax:
+                    self.just_ended[i] = True
                 continue
             if self.imitation:
                 a = int(target[i])
@@ -316,6 +340,14 @@ class EpisodePlanner:
                 prev = self.traj[i]['path'][-2][-1] if len(hop) == 1 else hop[-2]
                 view = next(c['pointId'] for c in obs[i]['scan_graph'].candidates(prev) if c['viewpointId'] == nxt)
                 moves.append((nxt, view))
+        if argmax:          # go back to the node with the best stop score (M/r2r/agent.py:665-672; dict order decides ties, as max() there)
+            for i in range(B):
+                if (not ended[i]) and self.just_ended[i] and gmaps[i].node_stop_scores:
+                    stop_node, score = max(gmaps[i].node_stop_scores.items(), key=lambda kv: kv[1]['stop'])
+                    if obs[i]['viewpoint'] != stop_node:
+                        self.traj[i]['path'].append(gmaps[i].graph.path(obs[i]['viewpoint'], stop_node))
+                    if te.objects is not None:
+                        self.traj[i]['pred_objid'] = score.get('og')
         self.obs = obs = te.sim.step(moves)
         for i, ob in enumerate(obs):
             if not ended[i]:

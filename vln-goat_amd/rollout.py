@@ -14,7 +14,7 @@ Here (M/ = /root/reference/map_nav_src), one module per layer, each importing on
   * rollout.py      (this module) `NavRollout`, the eager rollout loop, and the names of all the others: `rollout.<Name>` is the
                     public spelling of every class and function listed here.
   * episodes.py     planned episodes as shape-stable device work: `TeacherEpisode`, `EpisodePlanner`, `PlanWorker`, `EpisodeBuffers`.
-  * sampled.py      sampled walks over captured graphs: `SampledEpisode`, `SinglePassSampledEpisode`.
+  * sampled.py      sampled walks over captured graphs: `SampledEpisode`, `ArgmaxEpisode`, `SinglePassSampledEpisode`.
 
   * `NavRollout`                  the rollout loop (M/r2r/agent.py:448-676) for feedback = teacher / argmax / sample.  Teacher
                                   forcing needs no device->host copy at all (the next action comes from the ground-truth path), so the
@@ -31,7 +31,7 @@ from .nav_inputs import (language_inputs, panorama_inputs, panorama_object_input
                          teacher_object, teacher_action, start_walk, note_step, nodefault, fused_or_mean, pick_logits)
 from .episodes import (default_gmap_width, TeacherEpisode, _obj_concat_tables, EpisodePlanner, _RowIndex, _plan_worker_main,  # noqa: F401
                        PlanWorker, _pad1np, EpisodeBuffers)
-from .sampled import SampledEpisode, SinglePassSampledEpisode  # noqa: F401
+from .sampled import SampledEpisode, ArgmaxEpisode, SinglePassSampledEpisode  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ the rollout (agent.py:448-676)

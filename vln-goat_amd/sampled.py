@@ -3,6 +3,8 @@ replayed over the buffers of a `TeacherEpisode` (episodes.py).  The top layer: o
 
   * `SampledEpisode`              pass 1 of the two-pass form (M/r2r/agent.py:436-437,575-607): captured FORWARD graphs decide the
                                   walk; the finished plan then goes through the captured forward + backward body.
+  * `ArgmaxEpisode`               the validation walk (feedback = 'argmax'): the same step graphs in eval mode, the argmax, the stop score
+                                  and the best object of a step in one read-back; stop-node backtrack and `pred_objid` on the host.
   * `SinglePassSampledEpisode`    the reference's one-pass form (M/r2r/agent.py:596-690): the step graphs keep their autograd state
                                   and ONE captured backward graph differentiates the loss through all of them."""
 import gc
@@ -128,6 +130,91 @@ class SampledEpisode:
         plan = p.finish()
         self.host_s += time.perf_counter() - t0
         return plan, actions
+
+
+class ArgmaxEpisode:
+    """The validation walk (feedback = 'argmax': M/r2r/main_nav.py `valid` -> agent.test(), M/r2r/agent.py:575-672) as captured step
+    graphs over the buffers of a TeacherEpisode: the instruction graph and T step graphs of SampledEpisode, captured under no_grad with
+    the model in EVAL mode (an nn.Module's training flag is put back afterwards; a plain callable is taken as it is).  Each step graph
+    ends by writing [argmax, softmax[:, 0], best object index] into one static [3, B] float32 tensor with the torch ops NavRollout.run
+    uses — the step's only device -> host copy.  The host side (EpisodePlanner(feedback='argmax')) applies the argmax stop rule, records
+    the stop scores, appends the backtrack to the best stop node and fills `pred_objid`, exactly as NavRollout.run(feedback='argmax').
+
+        walk = ArgmaxEpisode(te, model, bufs, extras)             # captures T + 1 small graphs (bufs holds any valid plan)
+        traj = walk.run(episodes)                                  # [{'instr_id', 'path': [[vp], hop, ...], 'pred_objid'}]
+
+    The object holds no autograd state: it may be built before or after, and live beside, the training graphs of the process (TeacherEpisode
+    bodies, SampledEpisode) — unlike SinglePassSampledEpisode, whose step graphs keep their autograd graph alive and which therefore cannot
+    coexist with a second instance or a later training-step capture.  It shares `bufs` with whatever else replays over them: run() rewrites
+    the step tables, so load the training plan again before the next training replay."""
+
+    def __init__(self, te, model, bufs, extras=None):
+        self.te, self.bufs = te, bufs
+        extras = extras or {}
+        t_ = bufs.t
+        self.B = B = t_['txt_ids'].shape[0]
+        has_obj = te.objects is not None
+        self.back = torch.zeros(3, B, dtype=torch.float32, device=t_['txt_ids'].device)
+        module = model if isinstance(model, torch.nn.Module) else None
+        was_training = module.training if module is not None else False
+        if module is not None:
+            module.eval()
+        try:
+            self.g_lang, (self.txt, self.txt_kv) = SampledEpisode._capture(lambda: te._instruction(model, t_, extras, False))
+            nav_extras = te._nav_extras(extras, self.txt.dtype)
+            self.g_step = []
+            pool, last = [], None
+            for s in range(te.T):
+                def step(s=s, pool=pool, last=last):
+                    mine = list(pool)
+                    pano, pmask, fused = te._panoramas(model, t_, extras, 's%d_' % s, B, B)
+                    logits, new_last, obj_logits = te._nav_step(model, t_, s, self.txt, self.txt_kv, pano, pmask, fused, mine, last, nav_extras)
+                    probs = torch.softmax(logits.detach().float(), 1)
+                    rows = [probs.argmax(1).to(torch.float32), probs[:, 0].detach()]
+                    if has_obj:                 # the best object of every sample's current viewpoint (M/reverie/agent_obj_goat.py:680-690)
+                        vl = t_['s%d_view_lens' % s]
+                        pos = torch.arange(obj_logits.shape[1], device=obj_logits.device)[None, :]
+                        ol = torch.where(pos >= (vl + 2)[:, None], obj_logits.detach().float(), torch.full_like(obj_logits, -float('inf'), dtype=torch.float32))
+                        rows.append((ol.argmax(1) - (vl + 2)).to(torch.float32))
+                    else:
+                        rows.append(torch.zeros_like(rows[1]))
+                    self.back.copy_(torch.stack(rows, 0))
+                    return mine, new_last
+                g, (pool, last) = SampledEpisode._capture(step)
+                self.g_step.append(g)
+            self._keep = (pool, last)               # (the static outputs the later step graphs read)
+        finally:
+            if module is not None:
+                module.train(was_training)
+        self.host_s, self.steps, self.actions = 0.0, 0, []
+
+    def run(self, episodes):
+        """-> the trajectories of the argmax walk, one per episode: {'instr_id', 'path', and with objects 'pred_objid'}."""
+        te, bufs = self.te, self.bufs
+        if len(episodes) != self.B:
+            raise ValueError('ArgmaxEpisode: %d episodes for graphs captured at B = %d' % (len(episodes), self.B))
+        t0 = time.perf_counter()
+        p = EpisodePlanner(te, episodes, imitation=False, feedback='argmax')
+        self.host_s = time.perf_counter() - t0
+        bufs.load_part({'txt_ids': p.out['txt_ids'], 'txt_masks': p.out['txt_masks']})
+        self.g_lang.replay()
+        self.actions = []
+        for t in range(te.T):
+            t0 = time.perf_counter()
+            part = p.build_step()
+            self.host_s += time.perf_counter() - t0
+            bufs.load_part(part)
+            self.g_step[t].replay()
+            back = self.back.cpu().numpy()                    # (synchronises: the step's one read-back)
+            a = np.where(p.ended, 0, back[0].astype(np.int64))
+            self.actions.append(a)
+            t0 = time.perf_counter()
+            p.advance(a, back[1], back[2] if te.objects is not None else None)
+            self.host_s += time.perf_counter() - t0
+            if p.ended.all():
+                break
+        self.steps = len(self.actions)
+        return p.traj
 
 
 class SinglePassSampledEpisode:
