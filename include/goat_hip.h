@@ -50,7 +50,8 @@ int goat_version(void);
  *   dtype_in : element type of A, B, aux        dtype_out: element type of C (GOAT_F32 allowed with bf16 in)
  *   K and lda/ldb must be multiples of 16 bytes worth of elements (8 bf16 / 4 f32); bases 16-B aligned.
  *   split_k>1 : K is split over gridDim.y and partial tiles are atomically added into C (requires
- *               dtype_out==GOAT_F32, epilogue NONE, bias NULL; C must hold the value to accumulate onto).
+ *               dtype_out==GOAT_F32, epilogue NONE, bias NULL; C must hold the value to accumulate onto — also when
+ *               K is a single K-tile and nothing is left to split: a split_k>1 launch always ADDS into C).
  */
 int goat_gemm_nt(void* stream, int dtype_in, int dtype_out,
                  const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
@@ -72,7 +73,8 @@ int goat_gemm_nt(void* stream, int dtype_in, int dtype_out,
  *   every nn.Linear on the path (P/model/Bert_backbone.py:170-172,302,348,362; P/model/transformer.py:137-140).
  * bf16 inputs; dtype_out GOAT_BF16 or GOAT_F32 (F32 only with GOAT_EPI_NONE); the activation-derivative epilogues take no bias.  K-contiguous operands need
  * Kc % 64 == 0 (transposed operands: any Kc, the tail is zero-filled by the buffer bounds check); lda/ldb
- * multiples of 8, bases 16-B aligned, each operand < 2 GiB.  split_k>1: f32 atomic accumulation into C.
+ * multiples of 8, bases 16-B aligned, each operand < 2 GiB.  split_k>1: f32 atomic accumulation into C (split_k is clamped to the
+ * number of K-tiles; with one K-tile the launch runs unsplit and still adds into C).
  * bm: 64, 128 (four waves) or 256 (eight waves sharing one B tile: 25 % fewer L2->LDS bytes per flop, nstage <= 3; for
  * M >= 2048) — the M-tile; 64 fills the chip on small-M problems.  bm 128 with nstage | GOAT_GEMM_8WAVES: the 128-row tile
  * on eight waves (32x64 wave patches; twice the waves issue the tile's LDS-DMA).  nstage: 2..4 LDS ring stages (2 = most

@@ -252,10 +252,18 @@ __device__ __forceinline__ float dgelu_f(float x) {
 
 // bf16-grade erf-GELU for the GEMM epilogues whose result is rounded to bf16 anyway (GOAT_G2_FASTGELU, default on).
 // gelu(x) = x * (0.5 + s(xc)),  gelu'(x) = 0.5 + g(xc),  xc = clamp(x, -4, 4),  s, g odd polynomials of degree 15 (minimax fits
-// of Phi(x) - 0.5 and Phi(x) - 0.5 + x phi(x) on [0, 4]; |error| <= 4.4e-4 resp. 2.7e-4 absolute, i.e. 1/10 of a bf16
-// ulp at 1): 11 full-rate VALU operations instead of ~26 issue slots for the rcp + exp form above — the epilogue of a
-// 192x256 tile evaluates 49 152 of them with nothing else to hide behind.  The float32 parity path keeps gelu_f / dgelu_f.
-// minimax coefficients (tests/test_gelu_fit.py re-derives the error bounds)
+// of Phi(x) - 0.5 and Phi(x) - 0.5 + x phi(x) on [0, 4]): 11 full-rate VALU operations instead of ~26 issue slots for the
+// rcp + exp form above — the epilogue of a 192x256 tile evaluates 49 152 of them with nothing else to hide behind.  The
+// float32 parity path keeps gelu_f / dgelu_f.
+// Absolute error against float64 erf-GELU, over every finite bf16 input and a dense float32 grid on [-8, 8]
+// (tests/test_gelu_fit.py measures and asserts these, measured figure times 1.25):
+//   |gelu_fast(x)  - gelu(x)|  <= 5.7e-05 + 3.4e-04 * max(0, |x| - 4)
+//   |dgelu_fast(x) - gelu'(x)| <= 3.5e-04                        (1/10 of a bf16 ulp at 1)
+// gelu_fast is NOT bounded by a constant: outside the clamp it is x * (0.5 + s(+-4)), the residual of the fit at 4 (4e-5) times
+// |x|, while gelu itself has reached 0 resp. x — 3.2e-4 at x = -8, 2.5e-3 at -64, 4e-2 at -1000.  Harmless at BERT
+// pre-activation magnitudes and below the bf16 rounding of a positive result (2^-9 |x|); clamping the product instead would
+// cost two more VALU operations per element in an issue-bound epilogue.
+// minimax coefficients
 #define GOAT_GELU_C0 3.986733939e-01f
 #define GOAT_GELU_C1 -6.588784139e-02f
 #define GOAT_GELU_C2 9.505397558e-03f

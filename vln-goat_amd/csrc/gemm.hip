@@ -311,8 +311,12 @@ extern "C" int goat_gemm_nt(void* stream, int dtype_in, int dtype_out,
   a.tiles_n = (N + BN - 1) / BN;
   const int bk = BKB / (dtype_in == GOAT_BF16 ? 2 : 4);
   const int kt = (K + bk - 1) / bk;
+  const bool adds_into_c = split_k > 1;        // the contract of a split launch, whatever the clamp below leaves of it
   if (split_k < 1) split_k = 1;
   if (split_k > kt) split_k = kt;
+  // A contraction of one K-tile leaves nothing to split, but the launch must still ADD into C (it used to run the unsplit kernel and overwrite
+  // C: tests/test_gemm_family_gpu.py, K = 4 / 8 / 40 with split_k 2 onto a base).  Keep the atomic form: the second split is empty and returns.
+  if (adds_into_c && split_k == 1) split_k = 2;
   a.k_tiles_per_split = (kt + split_k - 1) / split_k;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype_in == GOAT_BF16) {

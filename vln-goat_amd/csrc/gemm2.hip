@@ -106,8 +106,12 @@ extern "C" int goat_gemm_bf16(void* stream, int trans_a, int trans_b, int dtype_
   a.accum = epilogue == GOAT_EPI_ACCUM;
   a.group_m = pick_group_m(a.tiles_m, a.tiles_n, bm, bn);
   const int kt = (Kc + BK - 1) / BK;
+  const bool adds_into_c = split_k > 1;        // the contract of a split launch, whatever the clamp below leaves of it
   if (split_k < 1) split_k = 1;
   if (split_k > kt) split_k = kt;
+  // A contraction of one K-tile leaves nothing to split: the launch runs unsplit, and must still ADD into C (it used to overwrite C:
+  // tests/test_gemm_family_gpu.py, Kc = 64 with split_k 2 / 3 onto a base).  float32 C without bias was checked above.
+  if (adds_into_c && split_k == 1) a.accum = 1;
   a.k_tiles_per_split = (kt + split_k - 1) / split_k;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (pp) return goat_g5_dispatch(st, a, bm, bn, trans_a, trans_b, dtype_out, epilogue, split_k, nstage, persist);
