@@ -28,7 +28,7 @@ def site(node):
             l = l.strip()
             if l.startswith('File') and ROOT in l and 'fanin_sites' not in l:
                 frames.append(l.replace(ROOT + '/', '').replace('File ', '').replace('"', ''))
-    outer = [f for f in frames if 'hipops.py' not in f]
+    outer = [f for f in frames if 'hipops.py' not in f and '/ops_' not in f]      # (the op layer: the facade and the family modules behind it)
     return ' <- '.join(([frames[-1]] if frames else ['?']) + outer[-2:][::-1])
 
 

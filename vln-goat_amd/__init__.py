@@ -1,8 +1,10 @@
 """vln-goat_amd — MI355X-native (gfx950) implementation of GOAT's cross-modal transformer hot path.
 
 Import as `vln_goat_amd` (the sibling alias package maps the importable name onto this directory).
-Contents: csrc/ (HIP kernels + C ABI), _lib.py (ctypes binding), hipops.py (autograd ops, GEMM autotuner, deferred grouped
-weight gradients), layers.py / pretrain_model.py / nav_model.py (reference-compatible nn.Module trees for pre-training
+Contents: csrc/ (HIP kernels + C ABI), _lib.py (ctypes binding), hipops.py (the op namespace: a facade over one module per op family —
+rng.py, ops_gemm.py, ops_linear.py, ops_norm.py, ops_attention.py, ops_dict.py, ops_embed.py, ops_heads.py — and over the layers below
+them: _plumbing.py, shadows.py, gradsink.py, tuning.py (GEMM autotuner), streams.py, wgrad_queue.py (deferred grouped weight
+gradients)), layers.py / pretrain_model.py / nav_model.py (reference-compatible nn.Module trees for pre-training
 and navigation fine-tuning), graphmap.py (host index building), dp.py (gradient arena + data-parallel engine over RCCL),
 synth.py (synthetic batches / episodes), frontdoor.py (FACL dictionaries: feature TSV, device k-means, cluster pick),
 backdoor.py (BACL dictionaries: token pick plan, running means on the device, room-type image dictionary),

@@ -1,5 +1,5 @@
-"""Pointer / dtype / stream helpers and the one launch path into the C ABI, shared by the modules that call it (hipops, tuning,
-wgrad_queue, optim)."""
+"""Pointer / dtype / stream / row-matrix helpers and the one launch path into the C ABI, shared by the modules that call it (the op
+families behind hipops, tuning, wgrad_queue, optim)."""
 import torch
 
 from . import _lib
@@ -27,8 +27,26 @@ def _need_gpu(t):
         raise RuntimeError('GOAT HIP ops need tensors on the GPU (no CPU fallback in the product path)')
 
 
+def _inference_only(what, *tensors):
+    for t in tensors:
+        if t is not None and t.requires_grad:
+            raise RuntimeError('%s is inference-only (no backward pass): got a tensor that requires grad — call it under '
+                               'torch.no_grad() on detached tensors' % what)
+    for t in tensors:
+        if t is not None:
+            _need_gpu(t)
+
+
 def _ptr(t, off=0):
     return t.data_ptr() + off * t.element_size()
+
+
+def _rows(x, dtype=None):
+    """x[..., H] as a contiguous [rows, H] matrix, cast to `dtype` (if given) before it is made contiguous."""
+    x2 = x.reshape(-1, x.shape[-1])
+    if dtype is not None and x2.dtype != dtype:
+        x2 = x2.to(dtype)
+    return x2.contiguous()
 
 
 # The per-argument test of cargs / launch, cheapest case first: plain values by exact type, tensors by exact type, and only then

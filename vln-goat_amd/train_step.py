@@ -12,6 +12,7 @@ The reference averages gradients over ranks inside DDP's backward hooks; here th
 backward of the accumulation window (GoatDataParallel.reduce_gradients with the gradient arena, GradBuckets without):
 the all-reduce is linear, so the result is the same.
 """
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -126,7 +127,6 @@ class PretrainStep:
         return info
 
 
-import numpy as np      # noqa: E402
 _NP_OF = {torch.float32: np.float32, torch.bfloat16: np.uint16, torch.float16: np.float16, torch.int64: np.int64, torch.int32: np.int32,
           torch.bool: np.bool_, torch.uint8: np.uint8}
 _INT_VIEW = {torch.bfloat16: torch.int16}        # numpy has no bfloat16: move the bits as 16-bit integers
