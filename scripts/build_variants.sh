@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build A/B variants of libgoat_hip.so: scripts/build_variants.sh name1:"-DX=1 -DY=2" name2:"..."  -> vln-goat_amd/csrc/ab/libgoat_<name>.so
-# (only gemm2.hip / gemm3.hip — or the sources named in VARIANT_SRC, e.g. VARIANT_SRC="rowops" — are recompiled with the extra
+# (only gemm2.hip / gemm3.hip — or the sources named in VARIANT_SRC, e.g. VARIANT_SRC="layernorm" — are recompiled with the extra
 #  flags; the other objects come from the regular build)
 set -e
 cd "$(dirname "$0")/../vln-goat_amd/csrc"

@@ -240,7 +240,7 @@ def _goat_rng_keep(seed, ctr, thr16):
 
 
 def flat_keep_mask(seed, offset, n, p):
-    """bool [n]: GoatRng(seed).keep(offset + i, goat_thr16(p)) for i < n — the mask of every row kernel of csrc/rowops.hip (dropout,
+    """bool [n]: GoatRng(seed).keep(offset + i, goat_thr16(p)) for i < n — the mask of every row kernel of csrc/dropout_act.hip and csrc/layernorm.hip (dropout,
     activation backward, LayerNorm input and output dropout), for BOTH dtypes: element i of the flat tensor owns counter offset + i
     (mod 2^64).  `seed` is the effective one (the call's seed + *rng_dev); any offset parity, counters of any size."""
     seed, offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)

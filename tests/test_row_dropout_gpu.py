@@ -1,4 +1,4 @@
-"""The training-mode dropout paths of csrc/rowops.hip outside attention — goat_dropout_add_fwd / goat_dropout_bwd, goat_act_bwd (and
+"""The training-mode dropout paths of csrc/dropout_act.hip and csrc/layernorm.hip (outside attention) — goat_dropout_add_fwd / goat_dropout_bwd, goat_act_bwd (and
 hipops.ffn with p > 0 on top of them), goat_ln_fwd_do / goat_ln_bwd_do in their generic forms and the bf16 768-wide backward — against
 float64 references on the upcast operands whose dropout masks come from helpers.flat_keep_mask, the host restatement of
 GoatRng::keep(offset + i, goat_thr16(p)).  No reference is built from anything a kernel wrote: a mask that forward and backward get
@@ -352,7 +352,7 @@ def check_ln_table(table=None):
         assert any(d == dt and M > 4096 and H == 256 for d, f, M, H, v in table)
         assert any(d == dt and (M, H, v) == (9, 768, 'deterministic') for d, f, M, H, v in table)
         assert any(d == dt and v == 'counter33' for d, f, M, H, v in table)
-        # MAXC 1, 2, 3, 4, 8 of csrc/rowops.hip's ln_maxc
+        # MAXC 1, 2, 3, 4, 8 of csrc/layernorm.hip's ln_maxc
         epc = 8 if dt == BF16 else 4
         maxc = {min(m for m in (1, 2, 3, 4, 8) if m >= (H // epc + 63) // 64) for H in WIDTHS[dt]}
         assert maxc == {1, 2, 3, 4, 8}, maxc

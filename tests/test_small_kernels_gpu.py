@@ -1,4 +1,4 @@
-"""The small non-GEMM kernels of csrc/causal.hip (attention pooling, door gate, dict_wsum, cfp_mix, InfoNCE, rowdot) and of csrc/rowops.hip
+"""The small non-GEMM kernels of csrc/causal.hip (attention pooling, door gate, dict_wsum, cfp_mix, InfoNCE, rowdot) and of csrc/embed.hip / csrc/linear_aux.hip
 (panorama fusion, short-K weight gradient, gather / segment mean, embedding tables, column sums) at every dispatch branch, width and tail,
 against float64 references on the CPU.
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/goat_hip.h"
 
 typedef __bf16 bf16_t;
@@ -65,6 +66,12 @@ template <> struct Chunk<float> {
     f32x4 t = {v[0], v[1], v[2], v[3]};
     goat_store_stream(reinterpret_cast<f32x4*>(p), t);
   }
+  __device__ __forceinline__ void add(const float* p) {      // v += the chunk at p
+    Chunk<float> t;
+    t.load(p);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] += t.v[i];
+  }
 };
 template <> struct Chunk<bf16_t> {
   float v[8];
@@ -84,6 +91,12 @@ template <> struct Chunk<bf16_t> {
 #pragma unroll
     for (int i = 0; i < 8; ++i) t[i] = (bf16_t)v[i];
     goat_store_stream(reinterpret_cast<f32x4*>(p), *reinterpret_cast<f32x4*>(&t));
+  }
+  __device__ __forceinline__ void add(const bf16_t* p) {
+    Chunk<bf16_t> t;
+    t.load(p);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] += t.v[i];
   }
 };
 
@@ -177,6 +190,26 @@ struct HeadRng {
 __host__ __device__ __forceinline__ uint32_t goat_thr16(float p) {
   return (uint32_t)(p * 65536.0f + 0.5f);
 }
+
+// The keep-mask of one dropout (p, seed, offset, device counter) as the row kernels use it: element i of the tensor is kept and
+// scaled by ks iff GoatRng(seed + *rng_dev).keep(offset + i).  Built once per thread; `on` is p > 0.
+struct DropMask {
+  GoatRng rng;
+  uint64_t offset;
+  uint32_t thr;
+  float ks;
+  bool on;
+  __device__ __forceinline__ DropMask(float p, uint64_t seed, uint64_t off, const uint64_t* rng_dev)
+      : rng(rng_dev ? seed + *rng_dev : seed), offset(off), thr(goat_thr16(p)), ks(p > 0.f ? 1.f / (1.f - p) : 1.f), on(p > 0.f) {}
+  // bit e = keep(i + e), e < N
+  template <int N>
+  __device__ __forceinline__ uint32_t bits(uint64_t i) const { return rng.keep_bits<N>(offset + i, thr); }
+  __device__ __forceinline__ bool keep(uint64_t i) const { return rng.keep(offset + i, thr); }
+  // element i: dropped or scaled
+  __device__ __forceinline__ void apply(float& v, uint64_t i) const {
+    if (on) v = keep(i) ? v * ks : 0.f;
+  }
+};
 
 // ---- wave64 reductions ---------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v) {
@@ -319,3 +352,10 @@ int dtype_dispatch(int dtype, F&& f) {
   return GOAT_E_ARG;
 }
 #define GOAT_DT_TYPE(dt_) typename decltype(dt_)::type
+
+// Calls f(std::true_type{}) or f(std::false_type{}): a run-time flag becomes `decltype(b)::value`, a template argument.  Nested
+// once per flag where a kernel is instantiated for every combination.
+template <typename F>
+int bool_dispatch(bool flag, F&& f) {
+  return flag ? f(std::true_type{}) : f(std::false_type{});
+}

@@ -2,6 +2,7 @@
 //   goat_add_n       : out = sum of up to 8 tensors, float32 accumulation, one rounding — the gradient fan-in of a tensor with several
 //                      consumers (hipops.fanout): one launch instead of the autograd engine's k - 1 pairwise `add` kernels
 //   goat_zero_ranges : up to 16 byte ranges cleared by one launch (the gradient arena's per-step fills: dp.GradArena.zero)
+// and the library's goat_version / goat_probe_tr16.
 #include "common.hpp"
 
 namespace {
@@ -14,16 +15,11 @@ __global__ __launch_bounds__(256) void add_n_kernel(AddNArgs a, T* __restrict__ 
   for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < nchunks; c += (int64_t)gridDim.x * 256) {
     const int64_t base = c * EPC;
     if (base + EPC <= numel) {
-      Chunk<T> acc, t;
+      Chunk<T> acc;
       acc.load(reinterpret_cast<const T*>(a.src[0]) + base);
 #pragma unroll
-      for (int i = 1; i < 8; ++i) {
-        if (i < a.n) {
-          t.load(reinterpret_cast<const T*>(a.src[i]) + base);
-#pragma unroll
-          for (int e = 0; e < EPC; ++e) acc.v[e] += t.v[e];
-        }
-      }
+      for (int i = 1; i < 8; ++i)
+        if (i < a.n) acc.add(reinterpret_cast<const T*>(a.src[i]) + base);
       acc.store_stream(out + base);
     } else {
       for (int64_t j = base; j < numel; ++j) {
@@ -49,7 +45,29 @@ __global__ __launch_bounds__(256) void zero_ranges_kernel(ZeroArgs a) {
   }
 }
 
+// ds_read_b64_tr_b16 probe: what the transposing LDS read hands each lane (goat_probe_tr16)
+__global__ void probe_tr16_kernel(uint16_t* out) {
+  __shared__ __attribute__((aligned(16))) uint16_t sm[64 * 4];
+  const int l = threadIdx.x;
+  for (int j = 0; j < 4; ++j) sm[l * 4 + j] = (uint16_t)(l * 4 + j);
+  __syncthreads();
+  typedef __attribute__((__vector_size__(4 * sizeof(short)))) short s16x4;
+  s16x4 t;
+  const uint32_t addr = (uint32_t)(uintptr_t)(sm + l * 4);
+  asm volatile("ds_read_b64_tr_b16 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(addr) : "memory");
+  for (int j = 0; j < 4; ++j) out[l * 4 + j] = (uint16_t)t[j];
+}
+
 }  // namespace
+
+extern "C" int goat_version(void) { return 105; }
+
+extern "C" int goat_probe_tr16(void* stream, uint16_t* out) {
+  if (!out) return GOAT_E_ARG;
+  hipLaunchKernelGGL(probe_tr16_kernel, dim3(1), dim3(64), 0, ST(stream), out);
+  GOAT_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int goat_add_n(void* stream, int dtype, const void* const* srcs, int n, void* out, int64_t numel) {
   if (!srcs || !out || n < 1 || n > 8) return GOAT_E_ARG;

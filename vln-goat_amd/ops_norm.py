@@ -1,5 +1,5 @@
 """Row kernels between the GEMMs: LayerNorm with its fused residual / dropout variants, dropout (+ residual), the gradient fan-in
-(add_n, fanout) and range fills.  Kernels: csrc/rowops.hip, csrc/glue.hip."""
+(add_n, fanout) and range fills.  Kernels: csrc/layernorm.hip, csrc/dropout_act.hip, csrc/glue.hip."""
 import ctypes
 import os
 
