@@ -605,6 +605,40 @@ int goat_nav_metrics(void* stream, const double* dist, const int64_t* scan_off, 
                      const int32_t* ref_start, const int32_t* goal, const int32_t* goal_start, int N, int max_ref, double margin,
                      double* out);
 
+/* ---- validation statistics of the pre-training tasks (csrc/valstats.hip) -----------------------------------------------------------
+ * The sums behind the reference's validate_mlm / _mrc / _sap / _cfp (P/train_r2r_goat.py:438-583) and validate_og
+ * (P/train_reverie_goat.py:587-612) without a host read per batch: goat_val_rows / goat_val_cfp write one loss and one hit per row,
+ * goat_val_reduce adds their sums into a float64 slot the caller reads once per loader.  Plain stores, no atomics, no waiting
+ * between workgroups: every sum has one writer and a fixed order, so two runs give the same bits (the reference's sums come out of
+ * float32 atomics).  Every entry returns GOAT_E_ARG / GOAT_E_SHAPE before any launch.
+ *
+ * goat_val_rows: logits float32 [M, ld] with N valid columns, ANY ld >= N and a base that needs float alignment only (16-byte loads
+ * where a row allows them; goat_ce_fwd demands ld % 4 == 0 and a 16-byte base, the [B, G] logits of sap / og have neither).  Each
+ * logit is read once.  Exactly one of `labels` (int64 [M]) and `soft` (float32 [M, ld_soft]) is non-null:
+ *   hard: row_loss[m] = logsumexp(row) - row[label], row_hit[m] = (argmax(row) == label): F.cross_entropy(reduction='sum') and
+ *         `scores.max(dim=-1)[1] == labels` (P/train_r2r_goat.py:449-451, :509-514; P/train_reverie_goat.py:597-599), row by row.
+ *         label < 0: an ignored row, loss 0, hit 0, not counted by goat_val_reduce.  label >= N: NaN loss, hit 0 (goat_ce_fwd's rule).
+ *   soft: row_loss[m] = sum_n xlogy(t, t) - t * log_softmax(row)[n] (F.kl_div(log_softmax, t, reduction='sum'), P/train_r2r_goat.py:
+ *         481-482; a zero target contributes 0), row_hit[m] = (argmax(row) == argmax(t)) (compute_accuracy_for_soft_targets, :466-470).
+ * Every argmax is the lowest index among the maxima.  -inf logits (masked slots) are skipped; a row of only -inf gives a NaN loss as
+ * torch does (its argmax is 0); a NaN logit gives a NaN loss and hit 0.  row_loss float32 [M], row_hit int32 [M].
+ * GOAT_E_ARG: null logits / row_loss / row_hit, both or neither of labels / soft; GOAT_E_SHAPE: M < 1, N < 1, ld < N, ld_soft < N. */
+int goat_val_rows(void* stream, const float* logits, int64_t ld, int M, int N, const int64_t* labels, const float* soft,
+                  int64_t ld_soft, float* row_loss, int32_t* row_hit);
+/* validate_cfp (P/train_r2r_goat.py:540-565): x is a HOST array of 3 device pointers (gmap, vp, fused), all operands float32 [B, H]
+ * packed.  row_loss[k, i] = 1/2 [CE(x_k[i]·txtᵀ/τ, i) + CE(txt[i]·x_kᵀ/τ, i)], row_hit[k, i] = (argmax_j x_k[i]·txt[j] == i) (image to
+ * text only, as the reference counts it; lowest index among the maxima); dots are float32 accumulations as in goat_infonce_fwd.
+ * row_loss float32 [3, B], row_hit int32 [3, B].  One workgroup per (k, i) holds both score rows in LDS: B <= GOAT_VAL_CFP_MAX_B.
+ * GOAT_E_ARG: a null pointer (x, any x[k], txt, row_loss, row_hit); GOAT_E_SHAPE: B < 1, B > 1024, H < 1, temperature not > 0. */
+#define GOAT_VAL_CFP_MAX_B 1024
+int goat_val_cfp(void* stream, const float* const* x, const float* txt, int B, int H, float temperature, float* row_loss,
+                 int32_t* row_hit);
+/* One workgroup: acc[0] += sum_m row_loss[m] (float64, strided partials in ascending order, then a fixed tree), acc[1] += sum_m
+ * row_hit[m], acc[2] += the number of rows with labels[m] >= 0 (labels NULL: M).  acc: one float64 [3] slot of a caller-owned
+ * [n_slots, 3] tensor; counts stay exact in a double.  Launches on one stream run in order, so a slot has one writer at a time.
+ * GOAT_E_ARG: null row_loss / row_hit / acc; GOAT_E_SHAPE: M < 1. */
+int goat_val_reduce(void* stream, const float* row_loss, const int32_t* row_hit, const int64_t* labels, int M, double* acc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ gradients)), layers.py / pretrain_model.py / nav_model.py (reference-compatible 
 and navigation fine-tuning), graphmap.py (host index building), dp.py (gradient arena + data-parallel engine over RCCL),
 synth.py (synthetic batches / episodes), frontdoor.py (FACL dictionaries: feature TSV, device k-means, cluster pick),
 backdoor.py (BACL dictionaries: token pick plan, running means on the device, room-type image dictionary),
+evaluate.py (navigation validation: eval_metrics on the device), pretrain_eval.py (pre-training validation: validate / validate_mlm /
+_mrc / _sap / _og / _cfp over device-side statistics),
 config.py, tuned_gfx950.json (autotuned GEMM table).
 """
 from .layers import compute_dtype, set_compute_dtype  # noqa: F401
@@ -16,5 +18,6 @@ from .frontdoor import (TIM_TSV_FIELDNAMES, DeviceKMeans, KMeansPicker, extract_
                         write_tim_tsv)
 from .backdoor import (InstrDictionaries, InstrPickPlan, build_img_zdict, img_zdict_keys, pick_positions,  # noqa: F401
                        write_img_zdict)
+from .pretrain_eval import ValStats, validate_cfp, validate_mlm, validate_mrc, validate_og, validate_sap  # noqa: F401
 
 __version__ = '0.1.0'

@@ -1,11 +1,11 @@
 """Heads and losses behind the encoders: per-row cross-entropy, the causal-learning heads (attention pooling, door gate, dictionary
-expectation), the SAP tail, and the CFP contrastive tail (mix + InfoNCE)."""
+expectation), the SAP tail, the CFP contrastive tail (mix + InfoNCE), and the validation statistics of the pre-training tasks."""
 import ctypes
 
 import torch
 
 from ._lib import GOAT_BF16, GOAT_F32
-from ._plumbing import _dt, _need_gpu, _ptr, _rows, launch
+from ._plumbing import _dt, _inference_only, _need_gpu, _ptr, _rows, launch
 from .gradsink import small_sinks
 from .ops_linear import _ce_rows_bwd, _ce_rows_fwd
 
@@ -358,3 +358,54 @@ def cfp_tail(go, vo, fwl, to, temperature):
 
 def infonce(g_loc, v_loc, f_loc, t_loc, g_all, v_all, f_all, t_all, target0, temperature):
     return _InfoNceFn.apply(g_loc, v_loc, f_loc, t_loc, g_all, v_all, f_all, t_all, target0, temperature)
+
+
+# ----------------------------------------------------------------------------- validation statistics (csrc/valstats.hip)
+def val_rows(logits, row_loss, row_hit, labels=None, soft=None):
+    """goat_val_rows: per-row loss and hit of logits [M, N] against hard labels (int64 [M]; negative = ignored row) or soft targets
+    (float32 [M, N]) into row_loss float32 [M] / row_hit int32 [M].  Rows may be strided (a column slice of a wider matrix is read in
+    place); anything else is made float32 and row-contiguous first.  -> the labels as the kernel read them (for val_reduce), or None."""
+    if (labels is None) == (soft is None):
+        raise ValueError('val_rows: exactly one of labels / soft')
+    _inference_only('val_rows', logits, labels, soft, row_loss, row_hit)
+    M, N = logits.shape
+    if logits.dtype != torch.float32 or logits.stride(1) != 1 or logits.stride(0) < N:
+        logits = logits.float().contiguous()
+    if labels is not None:
+        labels = labels.to(torch.int64).contiguous()
+        if labels.shape != (M,):
+            raise ValueError('val_rows: %d labels for %d rows' % (labels.numel(), M))
+    else:
+        if soft.shape != (M, N):
+            raise ValueError('val_rows: soft targets %s for logits %s' % (tuple(soft.shape), (M, N)))
+        if soft.dtype != torch.float32 or soft.stride(1) != 1 or soft.stride(0) < N:
+            soft = soft.float().contiguous()
+    if row_loss.dtype != torch.float32 or row_hit.dtype != torch.int32 or row_loss.numel() < M or row_hit.numel() < M \
+            or not (row_loss.is_contiguous() and row_hit.is_contiguous()):
+        raise ValueError('val_rows: row_loss float32 [>= M] and row_hit int32 [>= M], contiguous')
+    launch('goat_val_rows', logits, logits.stride(0), M, N, labels, soft, 0 if soft is None else soft.stride(0), row_loss, row_hit,
+           what='goat_val_rows(M=%d,N=%d)' % (M, N))
+    return labels
+
+
+def val_cfp(go, vo, fo, to, temperature, row_loss, row_hit):
+    """goat_val_cfp: row_loss / row_hit [3 * B] (modality-major: gmap, vp, fused) of the three image/text problems of validate_cfp"""
+    _inference_only('val_cfp', go, vo, fo, to, row_loss, row_hit)
+    ins = [t.float().contiguous() for t in (go, vo, fo, to)]
+    B, H = ins[0].shape
+    if any(t.shape != (B, H) for t in ins):
+        raise ValueError('val_cfp: four [B, H] operands, got %s' % [tuple(t.shape) for t in ins])
+    if row_loss.dtype != torch.float32 or row_hit.dtype != torch.int32 or row_loss.numel() < 3 * B or row_hit.numel() < 3 * B \
+            or not (row_loss.is_contiguous() and row_hit.is_contiguous()):
+        raise ValueError('val_cfp: row_loss float32 [>= 3 B] and row_hit int32 [>= 3 B], contiguous')
+    xs = (ctypes.c_void_p * 3)(*[_ptr(t) for t in ins[:3]])
+    launch('goat_val_cfp', xs, ins[3], B, H, float(temperature), row_loss, row_hit, what='goat_val_cfp(B=%d,H=%d)' % (B, H))
+
+
+def val_reduce(row_loss, row_hit, labels, acc):
+    """goat_val_reduce: acc (float64 [3], a slot of a wider accumulator) += (sum of row_loss, sum of row_hit, rows with label >= 0)"""
+    _inference_only('val_reduce', row_loss, row_hit, labels, acc)
+    M = row_loss.numel()
+    if acc.dtype != torch.float64 or acc.numel() != 3 or not acc.is_contiguous() or row_hit.numel() != M or (labels is not None and labels.numel() != M):
+        raise ValueError('val_reduce: acc float64 [3]; row_loss, row_hit and labels of one length')
+    launch('goat_val_reduce', row_loss, row_hit, labels, M, acc, what='goat_val_reduce(M=%d)' % M)

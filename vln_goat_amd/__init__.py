@@ -11,5 +11,6 @@ from .frontdoor import (TIM_TSV_FIELDNAMES, DeviceKMeans, KMeansPicker, extract_
                         write_tim_tsv)
 from .backdoor import (InstrDictionaries, InstrPickPlan, build_img_zdict, img_zdict_keys, pick_positions,  # noqa: E402,F401
                        write_img_zdict)
+from .pretrain_eval import ValStats, validate_cfp, validate_mlm, validate_mrc, validate_og, validate_sap  # noqa: E402,F401
 
 __version__ = '0.1.0'
