@@ -639,6 +639,59 @@ int goat_val_cfp(void* stream, const float* const* x, const float* txt, int B, i
  * GOAT_E_ARG: null row_loss / row_hit / acc; GOAT_E_SHAPE: M < 1. */
 int goat_val_reduce(void* stream, const float* row_loss, const int32_t* row_hit, const int64_t* labels, int M, double* acc);
 
+/* ---- the navigator of a policy-driven walk on the device (csrc/navstate.hip, csrc/navstate_core.hpp) --------------------------------
+ * A sampled (M/r2r/agent.py:596-690, feedback = 'sample') or argmax (:601-672) walk without host tables: goat_nav_step for index t
+ * does what EpisodePlanner.advance() of step t - 1 followed by build_step() of step t do on the host (vln-goat_amd/episodes.py:245-357;
+ * the map of M/models/graph_utils.py:43-144, the builders of M/r2r/agent.py:82-347, the fusion matrix of M/models/vilmodel_GOAT.py:
+ * 790-806) and writes the step's tables at the addresses the captured step graph reads.  t = 0 builds only; t = T advances only.
+ *   scan_tab   device int64 [14]: addresses of the static scan tables in the order navdev.ScanTables packs them (positions float64
+ *              [NV, 3]; candidate CSR start int32 [NV + 1], neighbour, pointId int32 [NC], normalized heading / elevation float64
+ *              [NC, 2], edge length float64 [NC]; feature row, scan of a viewpoint int32 [NV]; first viewpoint, size int32 [S], offset
+ *              int64 [S] and values float64 of the scans' all-pairs shortest distances; view_angle_feature_table float32 [36, 36, A];
+ *              heading / elevation of the 36 views float64 [36, 2]).  Viewpoints are numbered across the scans of the table.
+ *   step_tab   device int64 [21]: addresses of the tables of step t in the order feat_idx, feat_start, loc_fts, nav_types, view_lens,
+ *              gmap_step_ids, gmap_pos_fts, gmap_pair_dists, gmap_visited_masks, gmap_masks, vp_pos_fts, vp_masks, vp_nav_masks,
+ *              nav_fusion, target, csr_idx, csr_start, csr_scale, inv_idx, inv_start, inv_w, in the dtypes and shapes of
+ *              EpisodePlanner.build_step at map width G and panorama width W (int32 index tables, int64 ids / types / lens / target,
+ *              1-byte bool masks, float32 features).  Every element, padding included, is written.  NULL when t == T.
+ *   si, sd     the private state: B blocks of goat_nav_state_ints(T, W, cap) int32 and of cap * cap + cap float64 (distance matrix with
+ *              the reference's 95959595 default, stop scores).
+ *   log        the read-back block: actions int32 [T, B], alive flags [T, B], then B blocks of goat_nav_log_ints(T, cap) int32: a header
+ *              (word 2 ended, 5 status, 6 its step, 11 live steps, 16 hops, 17 / 18 start and length of the backtrack), T + 2 hop
+ *              starts and the hop log (viewpoint numbers).
+ *   ws         int32 workspace of 2 (B + 1) + T (B W + B) + B + 1 words; the last one holds the number of episodes still walking when
+ *              step t begins (for a caller that wants to stop early; reading it synchronises).
+ *   act        the action of step t - 1 (NULL at t = 0).  mode 0 (sample): the step's probabilities float32 [B, G_prev] with u float64
+ *              [T, B]: SampledEpisode.sample, a serial float64 cumulative sum in slot order, u * c[-1] clamped to nextafter(c[-1], 0),
+ *              the first slot whose cumulative mass exceeds it.  mode 1 (argmax): float32 [3, B] (action, stop score, best object);
+ *              the stop scores of live episodes are kept per node and an ending episode appends the path to the first maximum in visit
+ *              order.  mode 2 (forced): int32 [T, B].
+ * Status words (sticky, first wins): 1 a map larger than the step's bucket G or than cap, 2 a panorama wider than W, 3 an action that
+ * is not a selectable node, 4 a hop log or path stack that overflowed.  The kernel clamps and goes on; nothing faults.
+ * One workgroup per episode plus one workgroup for the batch-wide compact CSRs; plain stores, no atomics; float64 sums and
+ * comparisons are single IEEE operations (contraction off), so decisions, map distances and labels equal the host's bit for bit; the
+ * angle features go through the device's sin / cos / asin.
+ * PRECONDITION (the entry cannot read device memory): the address tables point at tensors of the stated sizes; ep holds valid numbers.
+ * GOAT_E_ARG: a null pointer (act / u where the mode and t need them, step_tab for t < T), a mode outside 0..2;
+ * GOAT_E_SHAPE: B, T, W, cap, G, G_prev of zero or above GOAT_NAV_MAX_*, G < 2 or G > cap + 2, t outside [0, T], A not a multiple of
+ * 4 in [4, 64].
+ * Both are returned before any launch. */
+#define GOAT_NAV_MAX_B 1024
+#define GOAT_NAV_MAX_T 64
+#define GOAT_NAV_MAX_G 256
+#define GOAT_NAV_MAX_W 64
+#define GOAT_NAV_MAX_CAP 254
+/* goat_nav_reset: start_walk (vln-goat_amd/nav_inputs.py:223-230) for B episodes: ep int32 [B, 4] = scan, start viewpoint, start view
+ * index, goal viewpoint.  Clears state and log, then the first update_graph. */
+/* sizes of one episode's blocks in int32 words (values, not status codes; 0 for sizes outside the limits above) */
+int goat_nav_state_ints(int T, int W, int cap);
+int goat_nav_log_ints(int T, int cap);
+int goat_nav_reset(void* stream, const int64_t* scan_tab, int32_t* si, double* sd, int32_t* log, const int32_t* ep, int B, int T, int W,
+                   int cap);
+int goat_nav_step(void* stream, const int64_t* scan_tab, const int64_t* step_tab, int32_t* si, double* sd, int32_t* log, int32_t* ws,
+                  const void* act, const double* u, int mode, int t, int B, int T, int G_prev, int G, int W, int A, int cap,
+                  int64_t ignoreid);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('GOAT_HIP_LIB') or os.path.join(CSRC, 'libgoat_hip.so')     # (override: kernel A/B experiments)
-SOURCES = ['gemm.hip', 'gemm2.hip', 'gemm3.hip', 'gemm5.hip', 'attention.hip', 'attention2.hip', 'attention_long.hip', 'decode.hip', 'kmeans.hip', 'zdict.hip', 'layernorm.hip', 'dropout_act.hip', 'linear_aux.hip', 'ce.hip', 'embed.hip', 'causal.hip', 'optim.hip', 'glue.hip', 'navmetrics.hip', 'valstats.hip']
+SOURCES = ['gemm.hip', 'gemm2.hip', 'gemm3.hip', 'gemm5.hip', 'attention.hip', 'attention2.hip', 'attention_long.hip', 'decode.hip', 'kmeans.hip', 'zdict.hip', 'layernorm.hip', 'dropout_act.hip', 'linear_aux.hip', 'ce.hip', 'embed.hip', 'causal.hip', 'optim.hip', 'glue.hip', 'navmetrics.hip', 'valstats.hip', 'navstate.hip']
 
 GOAT_F32, GOAT_BF16 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_ACCUM = 0, 1, 2, 3, 4, 5
@@ -94,6 +94,10 @@ SIGNATURES = {
     'goat_val_rows': [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp],
     'goat_val_cfp': [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp],
     'goat_val_reduce': [_vp, _vp, _vp, _vp, _i32, _vp],
+    'goat_nav_state_ints': [_i32, _i32, _i32],
+    'goat_nav_log_ints': [_i32, _i32],
+    'goat_nav_reset': [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32],
+    'goat_nav_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64],
 }
 
 

@@ -1,0 +1,95 @@
+// goat_nav_reset / goat_nav_step: the navigator of a policy-driven walk on the device, so that a sampled or argmax walk is one
+// loop of launches without a host table, a host decision or a read-back per step.  A step for index t does what the host planner's
+// EpisodePlanner.advance() of step t - 1 followed by build_step() of step t do (vln-goat_amd/episodes.py:245-357), which restate
+//   * the map:        GraphMap.update_graph / FloydGraph.add_edge, update, path        M/models/graph_utils.py:43-144
+//   * the move:       stop / no-node-left / last-step rules, make_equiv_action        M/r2r/agent.py:349-378,601-672
+//   * the action:     Categorical(probs).sample() as an inverse CDF, or the argmax    M/r2r/agent.py:629-660
+//   * the tables:     _panorama_feature_variable, _nav_gmap_variable, _nav_vp_variable, _teacher_action   M/r2r/agent.py:82-347
+//   * the logit fusion matrix                                                          M/models/vilmodel_GOAT.py:790-806
+// The text of all of it is csrc/navstate_core.hpp.
+//
+// This is latency-bound work on a few hundred values per episode, not bandwidth: ONE workgroup of 256 threads per episode.  The
+// order-dependent parts (node insertion, the action, path expansion, map order, the DAgger label) run on thread 0; the Floyd
+// relaxation over [n, n] and the [G], [G, G], [G, W + 2] and [W] tables are spread over the threads between barriers.  The state of an
+// episode stays in HBM / L2 between steps; the float64 distance matrix and the predecessor matrix are read there (at cap = 126 nodes
+// the two are 190 KB, more than a workgroup's LDS), the node lists and the header (a few KB) are copied into LDS for the step: the
+// serial parts are chains of dependent loads over them, each a fraction of a trip to L2 when it comes from LDS.  Every value
+// that must equal the host's bit for bit is one IEEE operation with contraction off.  A second launch of ONE workgroup forms the
+// batch-wide compact CSRs (prefix sums over the episodes, fixed order, no atomics).
+// Errors (a map wider than the bucket, a panorama wider than W, an action that is no selectable node) become a sticky status word
+// per episode; the kernel clamps and goes on.
+#include "common.hpp"
+
+#define NAV_HD __host__ __device__
+#include "navstate_core.hpp"
+
+namespace {
+
+using namespace navstate;
+
+struct DevSync {
+  __device__ void operator()() const { __syncthreads(); }
+};
+
+__global__ __launch_bounds__(256) void nav_reset_kernel(Args a, const int32_t* ep) {
+  reset_episode(a, ep, blockIdx.x, threadIdx.x, blockDim.x, DevSync());
+}
+
+// the node lists and the header of the episode are staged in LDS: the serial parts walk them in chains of dependent loads
+__global__ __launch_bounds__(256) void nav_step_kernel(Args a) {
+  extern __shared__ int32_t nav_lds[];
+  step_episode(a, blockIdx.x, threadIdx.x, blockDim.x, DevSync(), nav_lds);
+}
+
+__global__ __launch_bounds__(256) void nav_tail_kernel(Args a) {
+  __shared__ int32_t part[256];
+  nav_tail(a, part, threadIdx.x, blockDim.x, DevSync());
+}
+
+int nav_sizes_bad(int B, int T, int W, int cap) {
+  return B < 1 || B > GOAT_NAV_MAX_B || T < 1 || T > GOAT_NAV_MAX_T || W < 1 || W > GOAT_NAV_MAX_W || cap < 1 || cap > GOAT_NAV_MAX_CAP;
+}
+
+}  // namespace
+
+extern "C" int goat_nav_state_ints(int T, int W, int cap) { return nav_sizes_bad(1, T, W, cap) ? 0 : Layout(cap, T, W).ints; }
+extern "C" int goat_nav_log_ints(int T, int cap) { return nav_sizes_bad(1, T, 1, cap) ? 0 : Layout(cap, T, 1).log_ints; }
+
+extern "C" int goat_nav_reset(void* stream, const int64_t* scan_tab, int32_t* si, double* sd, int32_t* log, const int32_t* ep, int B,
+                              int T, int W, int cap) {
+  if (!scan_tab || !si || !sd || !log || !ep) return GOAT_E_ARG;
+  if (nav_sizes_bad(B, T, W, cap)) return GOAT_E_SHAPE;
+  Args a = {};
+  a.scan_tab = scan_tab;
+  a.si = si;
+  a.sd = sd;
+  a.log = log;
+  a.B = B;
+  a.T = T;
+  a.W = W;
+  a.cap = cap;
+  hipLaunchKernelGGL(nav_reset_kernel, dim3(B), dim3(256), 0, ST(stream), a, ep);
+  GOAT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int goat_nav_step(void* stream, const int64_t* scan_tab, const int64_t* step_tab, int32_t* si, double* sd, int32_t* log,
+                             int32_t* ws, const void* act, const double* u, int mode, int t, int B, int T, int G_prev, int G, int W, int A,
+                             int cap, int64_t ignoreid) {
+  if (!scan_tab || !si || !sd || !log || !ws) return GOAT_E_ARG;
+  if (nav_sizes_bad(B, T, W, cap) || t < 0 || t > T) return GOAT_E_SHAPE;
+  if (mode != MODE_SAMPLE && mode != MODE_ARGMAX && mode != MODE_FORCED) return GOAT_E_ARG;
+  if (t < T && !step_tab) return GOAT_E_ARG;
+  if (t > 0 && (!act || (mode == MODE_SAMPLE && !u))) return GOAT_E_ARG;
+  if (t < T && (G < 2 || G > GOAT_NAV_MAX_G || G > cap + 2 || A < 4 || A % 4 != 0 || A > 64)) return GOAT_E_SHAPE;
+  if (t > 0 && (G_prev < 2 || G_prev > GOAT_NAV_MAX_G)) return GOAT_E_SHAPE;
+  Args a = {scan_tab, step_tab, si, sd, log, ws, act, u, mode, t, B, T, G_prev, G, W, A, cap, ignoreid};
+  const size_t lds = (size_t)(Layout(cap, T, W).small + HDR) * sizeof(int32_t);      // <= 11 KB at the limits
+  hipLaunchKernelGGL(nav_step_kernel, dim3(B), dim3(256), lds, ST(stream), a);
+  GOAT_LAUNCH_CHECK();
+  if (t < T) {
+    hipLaunchKernelGGL(nav_tail_kernel, dim3(1), dim3(256), 0, ST(stream), a);
+    GOAT_LAUNCH_CHECK();
+  }
+  return 0;
+}

@@ -1,0 +1,697 @@
+// The navigator of a policy-driven walk, one episode at a time (csrc/navstate.hip launches it; the comment there says what it
+// restates).  Written against a thread index `tid` of `nt` cooperating threads and a `sync` callable, with no HIP type in it: the
+// kernels pass threadIdx / blockDim / __syncthreads, and the same text runs as ordinary C++ with (0, 1, no-op).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#ifndef NAV_HD
+#define NAV_HD
+#endif
+
+namespace navstate {
+
+constexpr double NAV_INF = 95959595.0;      // graph_utils.py:45
+constexpr int HDR = 32;
+// header words of an episode (the first HDR ints of its read-back block)
+enum { H_CUR = 0, H_VIEW, H_ENDED, H_JUST, H_N, H_STATUS, H_STATUS_T, H_START, H_GOAL, H_NOLEFT, H_NSCORED, H_LIVE, H_NSLOT, H_VLEN,
+       H_NCAND, H_STARTVIEW, H_HOPN, H_BT_START, H_BT_N, H_K, H_SCAN };
+enum { ST_OK = 0, ST_MAP = 1, ST_PANO = 2, ST_ACTION = 3, ST_PATH = 4 };
+enum { MODE_SAMPLE = 0, MODE_ARGMAX = 1, MODE_FORCED = 2 };
+enum { KIND_NONE = 0, KIND_SET = 1, KIND_ACC = 2 };
+// the static scan tables, in the order of the address table `scan_tab`
+enum { SC_POS = 0, SC_CAND_START, SC_CAND_NB, SC_CAND_POINT, SC_CAND_ANG, SC_CAND_LEN, SC_FEATURE_ROW, SC_VP_SCAN, SC_SCAN_OFF, SC_SCAN_N,
+       SC_DIST_OFF, SC_DIST, SC_VAF, SC_VIEW_ANG, SC_COUNT };
+// the tables of one step, in the order of the address table `step_tab`
+enum { TB_FEAT_IDX = 0, TB_FEAT_START, TB_LOC_FTS, TB_NAV_TYPES, TB_VIEW_LENS, TB_STEP_IDS, TB_GMAP_POS, TB_PAIR, TB_VISITED, TB_GMASK,
+       TB_VP_POS, TB_VP_MASK, TB_VP_NAV, TB_FUSION, TB_TARGET, TB_CSR_IDX, TB_CSR_START, TB_CSR_SCALE, TB_INV_IDX, TB_INV_START, TB_INV_W,
+       TB_COUNT };
+
+struct Layout {      // ints of an episode's private state / of its read-back block; navdev.py computes the same numbers
+  int cap, T, W, acc;
+  int o_vp, o_vis, o_step, o_kind, o_nacc, o_ord, o_slot, o_scored, o_iscand, o_acc, o_P, o_rows, o_cnode, o_seg, o_stk, small, ints;
+  int l_hs, l_hops, log_ints;
+  NAV_HD Layout(int cap_, int T_, int W_) : cap(cap_), T(T_), W(W_), acc(T_ + 1) {
+    int o = 0;
+    o_vp = o; o += cap;  o_vis = o; o += cap;  o_step = o; o += cap;  o_kind = o; o += cap;  o_nacc = o; o += cap;
+    o_ord = o; o += cap;  o_slot = o; o += cap;  o_scored = o; o += cap;  o_iscand = o; o += cap;
+    o_rows = o; o += W;  o_cnode = o; o += W;
+    o_seg = o; o += cap + 3;
+    small = o;           // everything above is what the serial parts of a step walk over: a kernel may stage it in LDS
+    o_acc = o; o += cap * acc;
+    o_P = o; o += cap * cap;
+    o_stk = o; o += 2 * cap + 2;
+    ints = o;
+    l_hs = HDR;  l_hops = l_hs + T + 2;  log_ints = l_hops + (T + 1) * cap;
+  }
+};
+
+struct Args {
+  const int64_t* scan_tab;
+  const int64_t* step_tab;      // null when t == T
+  int32_t* si;
+  double* sd;
+  int32_t* log;                 // [2 * T * B] actions, alive, then B read-back blocks
+  int32_t* ws;                  // workspace of the batch-wide tail
+  const void* act;
+  const double* u;
+  int mode, t, B, T, Gp, G, W, A, cap;
+  int64_t ignoreid;
+};
+
+template <class T> NAV_HD inline const T* scan_ptr(const Args& a, int k) { return reinterpret_cast<const T*>(a.scan_tab[k]); }
+template <class T> NAV_HD inline T* step_ptr(const Args& a, int k) { return reinterpret_cast<T*>(a.step_tab[k]); }
+
+struct Ep {       // the views of one episode's state
+  Layout L;
+  int32_t* S;       // the small arrays (offsets below L.small) and, in H, the header: global memory, or a staged copy of both
+  int32_t* Sb;      // the episode's block in global memory: node rows, predecessor matrix, path stack
+  int32_t* H;
+  int32_t* hs;
+  int32_t* hops;
+  double* D;
+  double* score;
+  int cap;
+  NAV_HD Ep(const Args& a, int b, int32_t* staged = nullptr) : L(a.cap, a.T, a.W), cap(a.cap) {
+    Sb = a.si + (int64_t)b * L.ints;
+    int32_t* G = a.log + (int64_t)2 * a.T * a.B + (int64_t)b * L.log_ints;
+    S = staged ? staged : Sb;
+    H = staged ? staged + L.small : G;
+    hs = G + L.l_hs;
+    hops = G + L.l_hops;
+    D = a.sd + (int64_t)b * ((int64_t)a.cap * a.cap + a.cap);
+    score = D + (int64_t)a.cap * a.cap;
+  }
+  NAV_HD void fail(int code, int t) const {
+    if (H[H_STATUS] == ST_OK) {
+      H[H_STATUS] = code;
+      H[H_STATUS_T] = t;
+    }
+  }
+  NAV_HD int find(int vp) const {
+    const int n = H[H_N];
+    for (int i = 0; i < n; ++i)
+      if (S[L.o_vp + i] == vp) return i;
+    return -1;
+  }
+  NAV_HD int find_or_add(int vp, int t) const {          // FloydGraph._ix / node_positions[vp] = ...: insertion order
+    int i = find(vp);
+    if (i >= 0) return i;
+    const int n = H[H_N];
+    if (n >= cap) {
+      fail(ST_MAP, t);
+      return -1;
+    }
+    S[L.o_vp + n] = vp;
+    H[H_N] = n + 1;
+    return n;
+  }
+};
+
+// FloydGraph.path (navsim.py:152-159; M/models/graph_utils.py:75-88) from node i to node j under the CURRENT _point matrix, iteratively:
+// the pending right halves wait on a stack of at most `nstk` entries.  emit(node) is called for every hop in order.  -> hops, or -1.
+template <class Emit>
+NAV_HD inline int expand_path(const int32_t* P, int cap, int i, int j, int32_t* stk, int nstk, Emit emit) {
+  int sp = 0, hops = 0, guard = 0;
+  for (;;) {
+    if (++guard > 8 * cap + 8) return -1;
+    if (i != j) {
+      const int k = P[i * cap + j];
+      if (k >= 0) {
+        if (sp >= nstk) return -1;
+        stk[sp++] = k * 256 + j;      // path(k, j) follows path(i, k)
+        j = k;
+        continue;
+      }
+      emit(j);
+      ++hops;
+    }
+    if (sp == 0) return hops;
+    const int e = stk[--sp];
+    i = e / 256;
+    j = e % 256;
+  }
+}
+
+// GraphMap.update_graph (navsim.py:180-189; graph_utils.py:100-111) for the viewpoint the episode stands on.  Collective.
+template <class Sync>
+NAV_HD inline void update_graph(const Args& a, const Ep& e, int t, int tid, int nt, Sync sync) {
+#pragma clang fp contract(off)
+  const int cap = e.cap;
+  int32_t* P = e.Sb + e.L.o_P;
+  if (tid == 0) {
+    const int32_t* cs = scan_ptr<int32_t>(a, SC_CAND_START);
+    const int32_t* nb = scan_ptr<int32_t>(a, SC_CAND_NB);
+    const double* len = scan_ptr<double>(a, SC_CAND_LEN);
+    const int v = e.H[H_CUR];
+    const int k = e.find_or_add(v, t);
+    e.H[H_K] = k;
+    if (k >= 0) {
+      for (int c = cs[v]; c < cs[v + 1]; ++c) {
+        const int j = e.find_or_add(nb[c], t);
+        if (j < 0) continue;
+        const double d = len[c];
+        if (d < e.D[k * cap + j]) {         // FloydGraph.add_edge
+          e.D[k * cap + j] = e.D[j * cap + k] = d;
+          P[k * cap + j] = P[j * cap + k] = -1;
+        }
+      }
+    }
+  }
+  sync();
+  const int n = e.H[H_N], k = e.H[H_K];
+  if (k >= 0) {
+    // FloydGraph.update(k): row and column k cannot improve (D[k][k] keeps the default), so the relaxation reads nothing it writes
+    for (int x = tid; x < n * n; x += nt) {
+      const int i = x / n, j = x % n;
+      if (i == j) continue;
+      const double c = e.D[i * cap + k] + e.D[k * cap + j];
+      if (c < e.D[i * cap + j]) {
+        e.D[i * cap + j] = c;
+        P[i * cap + j] = k;
+      }
+    }
+    if (tid == 0) e.S[e.L.o_vis + k] = 1;
+  }
+  sync();
+}
+
+// start_walk (nav_inputs.py:223-230): a fresh map, the first update_graph.  Collective.
+template <class Sync>
+NAV_HD inline void reset_episode(const Args& a, const int32_t* ep, int b, int tid, int nt, Sync sync) {
+  Ep e(a, b);
+  const int cap = a.cap;
+  for (int x = tid; x < e.L.ints; x += nt) e.S[x] = (x >= e.L.o_P && x < e.L.o_P + cap * cap) ? -1 : 0;
+  for (int x = tid; x < cap * cap + cap; x += nt) e.D[x] = x < cap * cap ? NAV_INF : 0.0;
+  for (int x = tid; x < e.L.log_ints; x += nt) e.H[x] = 0;
+  for (int x = tid; x < 2 * a.T; x += nt) a.log[(int64_t)x * a.B + b] = 0;
+  sync();
+  if (tid == 0) {
+    e.H[H_SCAN] = ep[b * 4 + 0];
+    e.H[H_CUR] = e.H[H_START] = ep[b * 4 + 1];
+    e.H[H_VIEW] = e.H[H_STARTVIEW] = ep[b * 4 + 2];
+    e.H[H_GOAL] = ep[b * 4 + 3];
+  }
+  sync();
+  update_graph(a, e, 0, tid, nt, sync);
+}
+
+NAV_HD inline double toward_zero(double c) {        // numpy.nextafter(c, 0.0)
+  if (c == 0.0 || c != c) return c;
+  int64_t bits;
+  memcpy(&bits, &c, 8);
+  bits -= 1;
+  memcpy(&c, &bits, 8);
+  return c;
+}
+
+// EpisodePlanner.advance of step tp (episodes.py:300-357) with the action of the mode.  Collective.
+template <class Sync>
+NAV_HD inline void advance_episode(const Args& a, const Ep& e, int b, int tp, int tid, int nt, Sync sync) {
+#pragma clang fp contract(off)
+  const int cap = a.cap;
+  const int ended = e.H[H_ENDED];
+  sync();
+  if (tid == 0) {
+    const int32_t* P = e.Sb + e.L.o_P;
+    const int cur = e.H[H_CUR];
+    const bool argmax = a.mode == MODE_ARGMAX;
+    int act = 0;
+    if (a.mode == MODE_SAMPLE) {           // SampledEpisode.sample (sampled.py:115-121): float64 cumulative sum in slot order
+      const float* p = reinterpret_cast<const float*>(a.act) + (int64_t)b * a.Gp;
+      double total = 0.0;
+      for (int g = 0; g < a.Gp; ++g) total = total + (double)p[g];
+      const double lim = toward_zero(total);
+      double x = a.u[(int64_t)tp * a.B + b] * total;
+      if (lim < x) x = lim;
+      double c = 0.0;
+      act = a.Gp;
+      for (int g = 0; g < a.Gp; ++g) {
+        c = c + (double)p[g];
+        if (c > x) {
+          act = g;
+          break;
+        }
+      }
+      if (ended) act = 0;
+    } else if (argmax) {
+      const float* back = reinterpret_cast<const float*>(a.act);
+      act = ended ? 0 : (int)back[b];
+      if (!ended) {                         // node_stop_scores[viewpoint] = {'stop': score}
+        const int ci = e.find(cur);
+        if (ci >= 0) {
+          bool seen = false;
+          for (int i = 0; i < e.H[H_NSCORED]; ++i) seen = seen || e.S[e.L.o_scored + i] == ci;
+          if (!seen) e.S[e.L.o_scored + e.H[H_NSCORED]++] = ci;
+          e.score[ci] = (double)back[a.B + b];
+        }
+      }
+    } else {
+      act = reinterpret_cast<const int32_t*>(a.act)[(int64_t)tp * a.B + b];
+    }
+    a.log[(int64_t)tp * a.B + b] = act;
+    a.log[(int64_t)(a.T + tp) * a.B + b] = !ended;
+    const bool stop = argmax ? act == 0 : cur == e.H[H_GOAL];
+    int dest = -1, view = e.H[H_VIEW];
+    int hopn = e.H[H_HOPN];
+    if (stop || ended || e.H[H_NOLEFT] || tp == a.T - 1) {
+      if (argmax) e.H[H_JUST] = 1;
+    } else {
+      const int nslots = e.H[H_NSLOT];
+      if (act < 0 || act >= nslots || act == 1 || (act > 1 && e.S[e.L.o_vis + e.S[e.L.o_ord + act - 2]])) {
+        e.fail(ST_ACTION, tp);                 // the host planner raises here; the walk goes on as if the episode had stopped
+      } else if (act >= 2) {
+        const int ci = e.find(cur), dn = e.S[e.L.o_ord + act - 2];
+        const int room = (a.T + 1) * cap - hopn;
+        int wrote = 0;
+        int32_t* out = e.hops + hopn;
+        const int32_t* vp = e.S + e.L.o_vp;
+        const int n = ci < 0 ? -1 : expand_path(P, cap, ci, dn, e.Sb + e.L.o_stk, 2 * cap + 2, [&](int node) {
+          if (wrote < room) out[wrote] = vp[node];
+          ++wrote;
+        });
+        if (n < 1 || wrote > room) {
+          e.fail(ST_PATH, tp);
+        } else {
+          dest = vp[dn];
+          const int prev = n == 1 ? cur : out[n - 2];
+          const int32_t* cs = scan_ptr<int32_t>(a, SC_CAND_START);
+          const int32_t* nb = scan_ptr<int32_t>(a, SC_CAND_NB);
+          const int32_t* pt = scan_ptr<int32_t>(a, SC_CAND_POINT);
+          bool found = false;
+          for (int c = cs[prev]; c < cs[prev + 1] && !found; ++c)
+            if (nb[c] == dest) {
+              view = pt[c];
+              found = true;
+            }
+          if (!found) e.fail(ST_PATH, tp);
+          hopn += n;
+        }
+      }
+    }
+    e.hs[tp + 1] = ended ? e.hs[tp] : hopn;       // (the backtrack's hops lie behind the last move's: no step owns them)
+    if (argmax && !ended && e.H[H_JUST] && e.H[H_NSCORED] > 0) {       // back to the best stop node: the first maximum in visit order
+      int best = e.S[e.L.o_scored];
+      for (int i = 1; i < e.H[H_NSCORED]; ++i) {
+        const int c = e.S[e.L.o_scored + i];
+        if (e.score[c] > e.score[best]) best = c;
+      }
+      const int ci = e.find(cur);
+      if (ci >= 0 && best != ci) {
+        const int room = (a.T + 1) * cap - hopn;
+        int wrote = 0;
+        int32_t* out = e.hops + hopn;
+        const int32_t* vp = e.S + e.L.o_vp;
+        const int n = expand_path(P, cap, ci, best, e.Sb + e.L.o_stk, 2 * cap + 2, [&](int node) {
+          if (wrote < room) out[wrote] = vp[node];
+          ++wrote;
+        });
+        if (n < 1 || wrote > room) {
+          e.fail(ST_PATH, tp);
+        } else {
+          e.H[H_BT_START] = hopn;
+          e.H[H_BT_N] = n;
+          hopn += n;
+        }
+      }
+    }
+    e.H[H_HOPN] = hopn;
+    if (dest >= 0) {
+      e.H[H_CUR] = dest;
+      e.H[H_VIEW] = view;
+    }
+    e.H[H_K] = dest;
+  }
+  sync();
+  const int moved = e.H[H_K] >= 0;
+  sync();
+  if (!ended) update_graph(a, e, tp, tid, nt, sync);
+  if (tid == 0) e.H[H_ENDED] = ended || !moved;
+  sync();
+}
+
+NAV_HD inline void angle_row(float* out, int A, double h, double el) {        // navsim.angle_feature
+  const float f[4] = {(float)sin(h), (float)cos(h), (float)sin(el), (float)cos(el)};
+  for (int x = 0; x < A; ++x) out[x] = f[x % 4];
+}
+
+// EpisodePlanner.build_step of step t (episodes.py:245-298) for one episode: every table row of the episode except the batch-wide
+// compact CSRs, whose pieces it leaves in the state for nav_tail.  Collective.
+template <class Sync>
+NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int nt, Sync sync) {
+#pragma clang fp contract(off)
+  const int cap = a.cap, t = a.t, B = a.B, G = a.G, W = a.W, A = a.A, C = a.A + 3;
+  const Layout& L = e.L;
+  int32_t* S = e.S;
+  const int32_t* cs = scan_ptr<int32_t>(a, SC_CAND_START);
+  const int32_t* nb = scan_ptr<int32_t>(a, SC_CAND_NB);
+  const int32_t* pt = scan_ptr<int32_t>(a, SC_CAND_POINT);
+  const int ended = e.H[H_ENDED], cur = e.H[H_CUR], view = e.H[H_VIEW];
+  const int c0 = cs[cur];
+  const int view_base = t * (B * W + B), fused_base = view_base + B * W;
+  if (tid == 0) {
+    if (!ended) e.H[H_LIVE] += 1;
+    // panorama_inputs: the candidates' views, then the views no candidate used
+    const int fr = scan_ptr<int32_t>(a, SC_FEATURE_ROW)[cur];
+    const int ncand = cs[cur + 1] - c0;
+    uint64_t used = 0;
+    int len = 0;
+    for (int c = 0; c < ncand; ++c) {
+      if (len < W) S[L.o_rows + len] = fr * 36 + pt[c0 + c];
+      used |= (uint64_t)1 << pt[c0 + c];
+      ++len;
+    }
+    for (int k = 0; k < 36; ++k)
+      if (!((used >> k) & 1)) {
+        if (len < W) S[L.o_rows + len] = fr * 36 + k;
+        ++len;
+      }
+    if (len > W) {
+      e.fail(ST_PANO, t);
+      len = W;
+    }
+    e.H[H_VLEN] = len;
+    e.H[H_NCAND] = ncand < W ? ncand : W;
+    // note_step (nav_inputs.py:233-243)
+    const int n = e.H[H_N];
+    for (int i = 0; i < n; ++i) S[L.o_iscand + i] = 0;
+    const int ci = e.find(cur);
+    if (!ended && ci >= 0) {
+      S[L.o_step + ci] = t + 1;
+      S[L.o_kind + ci] = KIND_SET;
+      S[L.o_nacc + ci] = 1;
+      e.Sb[L.o_acc + ci * L.acc] = fused_base + b;
+    }
+    for (int c = 0; c < e.H[H_NCAND]; ++c) {
+      const int j = e.find(nb[c0 + c]);
+      S[L.o_cnode + c] = j;
+      if (j < 0) continue;
+      S[L.o_iscand + j] = 1;
+      if (!ended && !S[L.o_vis + j]) {            // NodeEmbedStore.accumulate
+        const int row = view_base + b * W + c;
+        int32_t* acc = e.Sb + L.o_acc + j * L.acc;
+        if (S[L.o_kind + j] == KIND_NONE) {
+          S[L.o_kind + j] = KIND_ACC;
+          S[L.o_nacc + j] = 1;
+          acc[0] = row;
+        } else if (S[L.o_nacc + j] < L.acc) {
+          S[L.o_kind + j] = KIND_ACC;
+          acc[S[L.o_nacc + j]++] = row;
+        } else {
+          e.fail(ST_PATH, t);
+        }
+      }
+    }
+    // gmap_order: [stop], [MEM], the visited nodes, the unvisited ones, each in insertion order
+    int nv = 0;
+    for (int i = 0; i < n; ++i)
+      if (S[L.o_vis + i]) S[L.o_ord + nv++] = i;
+    int nu = nv;
+    for (int i = 0; i < n; ++i)
+      if (!S[L.o_vis + i]) S[L.o_ord + nu++] = i;
+    for (int k = 0; k < n; ++k) S[L.o_slot + S[L.o_ord + k]] = k + 2;
+    e.H[H_NOLEFT] = nu == nv;
+    int nslots = n + 2;
+    if (nslots > G) {
+      e.fail(ST_MAP, t);
+      nslots = G;
+    }
+    e.H[H_NSLOT] = nslots;
+    // teacher_action(imitation_learning=False) (nav_inputs.py:205-218): strict <, the first minimum wins
+    int64_t target = a.ignoreid;
+    if (!ended) {
+      const int goal = e.H[H_GOAL];
+      if (cur == goal) {
+        target = 0;
+      } else {
+        const int s = e.H[H_SCAN];
+        const int off = scan_ptr<int32_t>(a, SC_SCAN_OFF)[s], ns = scan_ptr<int32_t>(a, SC_SCAN_N)[s];
+        const double* dist = scan_ptr<double>(a, SC_DIST) + scan_ptr<int64_t>(a, SC_DIST_OFF)[s];
+        double best = INFINITY;
+        for (int g = 2; g < nslots; ++g) {
+          const int node = S[L.o_ord + g - 2];
+          if (S[L.o_vis + node]) continue;
+          const int k = S[L.o_vp + node] - off;
+          const double d = dist[(int64_t)k * ns + (goal - off)] + dist[(int64_t)(cur - off) * ns + k];
+          if (d < best) {
+            best = d;
+            target = g;
+          }
+        }
+      }
+    }
+    step_ptr<int64_t>(a, TB_TARGET)[b] = target;
+    step_ptr<int64_t>(a, TB_VIEW_LENS)[b] = len;
+    // the episode's share of the node-embedding CSR (NodeEmbedStore.csr): tokens per slot as a running sum
+    int tok = 0;
+    S[L.o_seg] = 0;
+    for (int g = 0; g < G; ++g) {
+      int cnt = 0;
+      if (g == 1 && t > 0) cnt = 1;
+      else if (g >= 2 && g < nslots) cnt = S[L.o_nacc + S[L.o_ord + g - 2]];
+      tok += cnt;
+      S[L.o_seg + g + 1] = tok;
+    }
+  }
+  sync();
+  const int vlen = e.H[H_VLEN], ncand = e.H[H_NCAND], nslots = e.H[H_NSLOT], n = e.H[H_N];
+  const double* vang = scan_ptr<double>(a, SC_VIEW_ANG);
+  const double bh = vang[view * 2], be = vang[view * 2 + 1];
+  // ---- panorama tokens
+  {
+    const double* cang = scan_ptr<double>(a, SC_CAND_ANG);
+    const float* vaf = scan_ptr<float>(a, SC_VAF);
+    const int fr36 = scan_ptr<int32_t>(a, SC_FEATURE_ROW)[cur] * 36;
+    float* loc = step_ptr<float>(a, TB_LOC_FTS) + (int64_t)b * W * C;
+    int64_t* ty = step_ptr<int64_t>(a, TB_NAV_TYPES) + (int64_t)b * W;
+    uint8_t* vm = step_ptr<uint8_t>(a, TB_VP_MASK) + (int64_t)b * (W + 2);
+    uint8_t* vn = step_ptr<uint8_t>(a, TB_VP_NAV) + (int64_t)b * (W + 2);
+    for (int j = tid; j < W; j += nt) {
+      float* row = loc + j * C;
+      if (j < ncand) {
+        angle_row(row, A, cang[(c0 + j) * 2] - bh, cang[(c0 + j) * 2 + 1] - be);
+      } else if (j < vlen) {
+        const float* src = vaf + ((int64_t)view * 36 + (S[L.o_rows + j] - fr36)) * A;
+        for (int x = 0; x < A; ++x) row[x] = src[x];
+      } else {
+        for (int x = 0; x < A; ++x) row[x] = 0.0f;
+      }
+      for (int x = A; x < C; ++x) row[x] = j < vlen ? 1.0f : 0.0f;
+      ty[j] = j < ncand ? 1 : 0;
+    }
+    for (int j = tid; j < W + 2; j += nt) {
+      vm[j] = j < vlen + 2;
+      vn[j] = j == 0 ? 1 : (j == 1 ? 0 : (j - 2 < ncand));
+    }
+  }
+  // ---- map tokens (gmap_inputs, GraphMap.get_pos_fts / pair_dists)
+  {
+    const double* pos = scan_ptr<double>(a, SC_POS);
+    const int32_t* P = e.Sb + L.o_P;
+    int64_t* sid = step_ptr<int64_t>(a, TB_STEP_IDS) + (int64_t)b * G;
+    uint8_t* vmask = step_ptr<uint8_t>(a, TB_VISITED) + (int64_t)b * G;
+    uint8_t* gmask = step_ptr<uint8_t>(a, TB_GMASK) + (int64_t)b * G;
+    float* scale = step_ptr<float>(a, TB_CSR_SCALE) + (int64_t)b * G;
+    float* gp = step_ptr<float>(a, TB_GMAP_POS) + (int64_t)b * G * C;
+    const int ci = e.find(cur);
+    const double ax = pos[cur * 3], ay = pos[cur * 3 + 1], az = pos[cur * 3 + 2];
+    for (int g = tid; g < G; g += nt) {
+      float* row = gp + g * C;
+      const bool real = g >= 2 && g < nslots;
+      const int node = real ? S[L.o_ord + g - 2] : -1;
+      sid[g] = real ? S[L.o_step + node] : 0;
+      vmask[g] = g == 1 ? 1 : (real ? S[L.o_vis + node] != 0 : 0);
+      gmask[g] = g < nslots && g != 1;
+      scale[g] = (real && S[L.o_kind + node] == KIND_ACC) ? (float)(1.0 / (double)S[L.o_nacc + node]) : 1.0f;
+      if (g >= nslots) {
+        for (int x = 0; x < C; ++x) row[x] = 0.0f;
+        continue;
+      }
+      float h32 = 0.0f, e32 = 0.0f;
+      double line = 0.0, md = 0.0, hops = 0.0;
+      if (real) {
+        const int v = S[L.o_vp + node];
+        const double by = pos[v * 3 + 1];
+        const double dx = pos[v * 3] - ax, dy = by - ay, dz = pos[v * 3 + 2] - az;       // navsim.rel_pos
+        const double xy = fmax(sqrt(dx * dx + dy * dy), 1e-8);
+        const double xyz = fmax(sqrt(dx * dx + dy * dy + dz * dz), 1e-8);
+        double hd = asin(dx / xy);
+        if (by < ay) hd = 3.141592653589793 - hd;
+        const double el = asin(dz / xyz);
+        h32 = (float)(hd - bh);
+        e32 = (float)(el - be);
+        line = xyz / 30.0;
+        if (ci >= 0 && node != ci) {
+          md = e.D[ci * cap + node] / 30.0;
+          int32_t stk[256];
+          const int nh = expand_path(P, cap, ci, node, stk, 256, [](int) {});
+          hops = (double)(nh < 0 ? 0 : nh) / 10.0;
+        }
+      }
+      // get_angle_fts: sin / cos of the float32 angles
+      const float f[4] = {(float)sin((double)h32), (float)cos((double)h32), (float)sin((double)e32), (float)cos((double)e32)};
+      for (int x = 0; x < A; ++x) row[x] = f[x % 4];
+      row[A] = (float)line;
+      row[A + 1] = (float)md;
+      row[A + 2] = (float)hops;
+    }
+    float* pair = step_ptr<float>(a, TB_PAIR) + (int64_t)b * G * G;
+    for (int x = tid; x < G * G; x += nt) {
+      const int g = x / G, h = x % G;
+      float v = 0.0f;
+      if (g >= 2 && h >= 2 && g < nslots && h < nslots && g != h) v = (float)e.D[S[L.o_ord + g - 2] * cap + S[L.o_ord + h - 2]];
+      pair[x] = v;
+    }
+    // nav_fusion_matrix (nav_model.py:231-253)
+    float* fus = step_ptr<float>(a, TB_FUSION) + (int64_t)b * G * (W + 2);
+    for (int x = tid; x < G * (W + 2); x += nt) {
+      const int g = x / (W + 2), j = x % (W + 2);
+      float v = 0.0f;
+      if (g >= 2 && g < nslots && j >= 2 && j - 2 < ncand) {
+        const int node = S[L.o_ord + g - 2], cn = S[L.o_cnode + j - 2];
+        if (!S[L.o_vis + node] && cn >= 0) {
+          if (cn == node) v = 1.0f;
+          else if (S[L.o_vis + cn] && !S[L.o_iscand + node]) v = 1.0f;
+        }
+      }
+      fus[x] = v;
+    }
+  }
+  sync();
+  // ---- vp_inputs: the start node's row in every slot, the candidates' rows behind it (rows of gmap_pos_fts)
+  {
+    const float* gp = step_ptr<float>(a, TB_GMAP_POS) + (int64_t)b * G * C;
+    float* vp = step_ptr<float>(a, TB_VP_POS) + (int64_t)b * (W + 2) * 2 * C;
+    const int sn = e.find(e.H[H_START]);
+    const int sslot = sn >= 0 ? S[L.o_slot + sn] : G;
+    for (int x = tid; x < (W + 2) * 2 * C; x += nt) {
+      const int j = x / (2 * C), c = x % (2 * C);
+      float v = 0.0f;
+      if (c < C) {
+        if (sslot < nslots) v = gp[sslot * C + c];
+      } else if (j >= 2 && j - 2 < ncand) {
+        const int cn = S[L.o_cnode + j - 2];
+        const int slot = cn >= 0 ? S[L.o_slot + cn] : G;
+        if (slot < nslots) v = gp[slot * C + c - C];
+      }
+      vp[x] = v;
+    }
+  }
+  (void)n;
+}
+
+// One step of one episode: the move of step t - 1, then the tables of step t.
+template <class Sync>
+NAV_HD inline void step_episode(const Args& a, int b, int tid, int nt, Sync sync, int32_t* staged = nullptr) {
+  // staged: room for Layout::small + HDR ints all threads share (LDS).  The serial parts are chains of dependent loads over the node
+  // lists; from LDS each costs a fraction of a trip to L2.
+  Ep e(a, b, staged);
+  if (staged) {
+    Ep g(a, b);
+    for (int x = tid; x < e.L.small; x += nt) staged[x] = g.S[x];
+    for (int x = tid; x < HDR; x += nt) e.H[x] = g.H[x];
+    sync();
+  }
+  if (a.t > 0) advance_episode(a, e, b, a.t - 1, tid, nt, sync);
+  if (a.t < a.T) build_episode(a, e, b, tid, nt, sync);
+  if (staged) {
+    Ep g(a, b);
+    sync();
+    for (int x = tid; x < e.L.small; x += nt) g.S[x] = staged[x];
+    for (int x = tid; x < HDR; x += nt) g.H[x] = e.H[x];
+  }
+}
+
+// The batch-wide tail of a step: the compact CSRs are prefix sums over the episodes (episodes.py:_compact_rows, NodeEmbedStore.csr,
+// graphmap.inverse_index).  One group of threads; `part` holds nt ints they share.  ws: [2 * (B + 1)] bases, one owner per pool row, the live count.
+template <class Sync>
+NAV_HD inline void nav_tail(const Args& a, int32_t* part, int tid, int nt, Sync sync) {
+  const int B = a.B, G = a.G, W = a.W, t = a.t;
+  const int rows = (t + 1) * (B * W + B), n_src = rows + (t > 0 ? B : 0);
+  int32_t* fbase = a.ws;
+  int32_t* cbase = a.ws + B + 1;
+  int32_t* owner = a.ws + 2 * (B + 1);
+  int32_t* feat_idx = step_ptr<int32_t>(a, TB_FEAT_IDX);
+  int32_t* feat_start = step_ptr<int32_t>(a, TB_FEAT_START);
+  int32_t* csr_idx = step_ptr<int32_t>(a, TB_CSR_IDX);
+  int32_t* csr_start = step_ptr<int32_t>(a, TB_CSR_START);
+  const float* csr_scale = step_ptr<float>(a, TB_CSR_SCALE);
+  int32_t* inv_idx = step_ptr<int32_t>(a, TB_INV_IDX);
+  int32_t* inv_start = step_ptr<int32_t>(a, TB_INV_START);
+  float* inv_w = step_ptr<float>(a, TB_INV_W);
+  if (tid == 0) {
+    int f = 0, c = 0, live = 0;
+    for (int b = 0; b < B; ++b) {
+      Ep e(a, b);
+      fbase[b] = f;
+      cbase[b] = c;
+      f += e.H[H_VLEN];
+      c += e.S[e.L.o_seg + G];
+      live += !e.H[H_ENDED];
+    }
+    fbase[B] = f;
+    cbase[B] = c;
+    a.ws[2 * (B + 1) + a.T * (B * W + B) + B] = live;      // episodes still walking when step t begins (an optional host read)
+  }
+  for (int r = tid; r < n_src; r += nt) owner[r] = -1;
+  sync();
+  const int ftot = fbase[B], ctot = cbase[B];
+  for (int s = tid; s < B * W; s += nt) {
+    const int b = s / W, j = s % W;
+    Ep e(a, b);
+    const int vl = e.H[H_VLEN];
+    feat_start[s] = fbase[b] + (j < vl ? j : vl);
+    if (j < vl) feat_idx[fbase[b] + j] = e.S[e.L.o_rows + j];
+    if (s >= ftot) feat_idx[s] = -1;
+  }
+  if (tid == 0) {
+    feat_start[B * W] = ftot;
+    csr_start[B * G] = ctot;
+    inv_start[n_src] = ctot;
+  }
+  for (int s = tid; s < B * G; s += nt) {
+    const int b = s / G, g = s % G;
+    Ep e(a, b);
+    const int lo = e.S[e.L.o_seg + g], cnt = e.S[e.L.o_seg + g + 1] - lo, at = cbase[b] + lo;
+    csr_start[s] = at;
+    if (cnt == 0) continue;
+    if (g == 1) {
+      csr_idx[at] = rows + b;
+      owner[rows + b] = s;
+    } else {
+      const int32_t* acc = e.S + e.L.o_acc + e.S[e.L.o_ord + g - 2] * e.L.acc;
+      for (int i = 0; i < cnt; ++i) {
+        const int r = acc[i];
+        csr_idx[at + i] = r;
+        if (r >= 0 && r < n_src) owner[r] = s;
+      }
+    }
+  }
+  for (int s = ctot + tid; s < n_src; s += nt) {
+    csr_idx[s] = -1;
+    inv_idx[s] = -1;
+    inv_w[s] = 0.0f;
+  }
+  sync();
+  // inverse index: a pool row is read by at most one segment, so "grouped by source row" is the order of the rows themselves
+  const int chunk = (n_src + nt - 1) / nt;
+  const int lo = tid * chunk < n_src ? tid * chunk : n_src, hi = lo + chunk < n_src ? lo + chunk : n_src;
+  int cnt = 0;
+  for (int r = lo; r < hi; ++r) cnt += owner[r] >= 0;
+  part[tid] = cnt;
+  sync();
+  int at = 0;
+  for (int i = 0; i < tid; ++i) at += part[i];
+  for (int r = lo; r < hi; ++r) {
+    inv_start[r] = at;
+    const int s = owner[r];
+    if (s >= 0 && at < n_src) {
+      inv_idx[at] = s;
+      inv_w[at] = csr_scale[s];
+      ++at;
+    }
+  }
+}
+
+}  // namespace navstate

@@ -76,18 +76,20 @@ def _prune_memo():
             del _MASK_MEMO[key]
 
 
-def refresh_masks(only=None):
+def refresh_masks(only=None, force=False):
     """recompute, into the same storage, every memoised mask whose source tensor was edited in place (insertion order: a mask
     derived from another memoised mask is refreshed after it).  Entries of dead tensors are dropped.
     only: the edited source tensors (views of one buffer share a version counter: after a PARTIAL copy into an EpisodeBuffers every
-    view looks edited) — just their masks, and the masks derived from those, are recomputed."""
+    view looks edited) — just their masks, and the masks derived from those, are recomputed.
+    force: recompute whatever the version counters say — the sources were written by a kernel launched outside torch
+    (navdev.DeviceNavigator), which bumps no counter."""
     ids = None if only is None else {id(t) for t in only}
     for key in list(_MASK_MEMO):
         ent = _MASK_MEMO[key]
         t = ent[0]()
         if t is None:
             del _MASK_MEMO[key]
-        elif ent[1] != t._version and (ids is None or id(t) in ids):
+        elif (force or ent[1] != t._version) and (ids is None or id(t) in ids):
             ent[2].copy_(ent[3](t))
             ent[1] = t._version
             if ids is not None:

@@ -1,0 +1,293 @@
+"""The navigator of a policy-driven walk on the DEVICE (overview: rollout.py; kernels: csrc/navstate.hip).
+
+A sampled walk (`sampled.SinglePassSampledEpisode`) and the validation walk (`sampled.ArgmaxEpisode`) are host-paced on the host
+planner: per step `EpisodePlanner.build_step()` builds about twenty small tables, `EpisodeBuffers.load_part` copies them, the step
+graph is replayed, the host reads the probabilities back (a synchronisation), picks the action and moves the Python navigator.  Here
+the navigator's state lives in HBM and `goat_nav_step` does advance() + build_step() in two launches that write the step's tables at
+the addresses the captured step graph reads: the walk is one loop of launches, without a device -> host copy or a synchronisation
+before its end.  The host planner stays as it is and is the reference this module is tested against.
+
+  * `ScanTables`        the static tables of a set of ScanGraphs (positions, candidate lists, edge lengths, shortest distances,
+                        feature rows, the view-angle table), built and uploaded once; `.host` holds them as numpy arrays.
+  * `DeviceNavigator`   the per-episode state block of one (B, T) bucket over an `EpisodeBuffers`, in one of three modes: 'sample'
+                        (SampledEpisode.sample restated on the device), 'argmax' (the stop rule, stop scores and backtrack of the
+                        validation walk) and 'forced' (a given [T, B] action tensor: TeacherEpisode.plan(actions=...)).
+
+Scope: R2R-style walks.  The REVERIE / SOON object tables (`te.objects`) stay on the host planner, and so does the two-pass
+`SampledEpisode`, which needs finish()'s joined `all_*` tables and is the slower form of the sampled half anyway."""
+import time
+
+import numpy as np
+import torch
+
+from . import _lib, layers
+from ._plumbing import launch
+from .nav_inputs import language_inputs
+from .navsim import GraphSim, view_angle_feature_table, view_angles
+
+MODES = {'sample': 0, 'argmax': 1, 'forced': 2}
+STATUS = {1: 'the map has more nodes than the bucket of the step holds', 2: 'the panorama is wider than the bucket W',
+          3: 'the action is not a selectable node of the map', 4: 'the hop log or a path stack overflowed'}
+# the order of the address tables (csrc/navstate_core.hpp)
+SCAN_TABLES = ('pos', 'cand_start', 'cand_nb', 'cand_point', 'cand_ang', 'cand_len', 'feature_row', 'vp_scan', 'scan_off', 'scan_n',
+               'dist_off', 'dist', 'vaf', 'view_ang')
+STEP_TABLES = (('feat_idx', torch.int32), ('feat_start', torch.int32), ('loc_fts', torch.float32), ('nav_types', torch.int64),
+               ('view_lens', torch.int64), ('gmap_step_ids', torch.int64), ('gmap_pos_fts', torch.float32), ('gmap_pair_dists', torch.float32),
+               ('gmap_visited_masks', torch.bool), ('gmap_masks', torch.bool), ('vp_pos_fts', torch.float32), ('vp_masks', torch.bool),
+               ('vp_nav_masks', torch.bool), ('nav_fusion', torch.float32), ('target', torch.int64), ('csr_idx', torch.int32),
+               ('csr_start', torch.int32), ('csr_scale', torch.float32), ('inv_idx', torch.int32), ('inv_start', torch.int32),
+               ('inv_w', torch.float32))
+H_ENDED, H_STATUS, H_STATUS_T, H_LIVE, H_HOPN, H_BT_START, H_BT_N, HDR = 2, 5, 6, 11, 16, 17, 18, 32
+MAX_B, MAX_T, MAX_G, MAX_W, MAX_CAP = 1024, 64, 256, 64, 254        # GOAT_NAV_MAX_* (include/goat_hip.h)
+
+
+class ScanTables:
+    """The read-only tables `goat_nav_step` walks on, for the ScanGraphs `scans`.  Viewpoints are numbered across the scans
+    (`first[scan name]` + the scan's own index); per viewpoint: position, the candidate list in the order of `ScanGraph.candidates(vp)`
+    (neighbour, pointId, normalized heading / elevation, and the edge length exactly as `GraphMap.update_graph` computes it) and the
+    feature row; per scan: the all-pairs distances of `ScanGraph.shortest()`.  row_of: `row(scan_name, vp) -> int` or an object with that
+    method (features.FeatureStore).  device=None keeps the tables on the host only (`.host`: {name: numpy array})."""
+
+    def __init__(self, scans, row_of, angle_feat_size=4, device='cuda'):
+        scans = list(scans.values() if isinstance(scans, dict) else scans)
+        row = row_of.row if hasattr(row_of, 'row') else row_of
+        self.scans, self.A = scans, angle_feat_size
+        self.ids = {sc.name: k for k, sc in enumerate(scans)}
+        self.first, self.names = {}, []
+        for sc in scans:
+            self.first[sc.name] = len(self.names)
+            self.names += list(sc.vpids)
+        pos, cstart, cnb, cpt, cang, clen, frow, vscan, dist, doff = [], [0], [], [], [], [], [], [], [], [0]
+        for k, sc in enumerate(scans):
+            off = self.first[sc.name]
+            for vp in sc.vpids:
+                p = np.asarray(tuple(float(x) for x in sc.pos[sc.index[vp]]), np.float64)
+                for c in sc.candidates(vp):
+                    d = np.asarray(c['position'], np.float64) - p
+                    clen.append(np.sqrt(d[0] ** 2 + d[1] ** 2 + d[2] ** 2))             # navsim.GraphMap.update_graph
+                    cnb.append(off + sc.index[c['viewpointId']])
+                    cpt.append(c['pointId'])
+                    cang.append((c['normalized_heading'], c['normalized_elevation']))
+                cstart.append(len(cnb))
+                frow.append(row(sc.name, vp))
+                vscan.append(k)
+            pos.append(sc.pos)
+            dist.append(np.asarray(sc.shortest()[0], np.float64).reshape(-1))
+            doff.append(doff[-1] + dist[-1].size)
+        self.host = {
+            'pos': np.concatenate(pos, 0).astype(np.float64), 'cand_start': np.asarray(cstart, np.int32), 'cand_nb': np.asarray(cnb, np.int32),
+            'cand_point': np.asarray(cpt, np.int32), 'cand_ang': np.asarray(cang, np.float64).reshape(-1, 2), 'cand_len': np.asarray(clen, np.float64),
+            'feature_row': np.asarray(frow, np.int32), 'vp_scan': np.asarray(vscan, np.int32),
+            'scan_off': np.asarray([self.first[sc.name] for sc in scans], np.int32), 'scan_n': np.asarray([len(sc.vpids) for sc in scans], np.int32),
+            'dist_off': np.asarray(doff[:-1], np.int64), 'dist': np.concatenate(dist), 'vaf': view_angle_feature_table(angle_feat_size),
+            'view_ang': np.asarray([view_angles(v) for v in range(36)], np.float64)}
+        self.device = None if device is None else torch.device(device)
+        self.dev, self.tab = None, None
+        if self.device is not None:
+            self._upload()
+
+    def vp(self, scan_name, vpid):
+        """the number of a viewpoint in these tables"""
+        sc = self.scans[self.ids[scan_name]]
+        return self.first[scan_name] + sc.index[vpid]
+
+    def _upload(self):
+        """one packed buffer, one H2D copy; `tab` = the addresses of the tables inside it (device int64 [14])"""
+        offs, n = [], 0
+        for name in SCAN_TABLES:
+            offs.append(n)
+            n += (max(self.host[name].nbytes, 1) + 15) // 16 * 16
+        flat = torch.zeros(n, dtype=torch.uint8)
+        for name, o in zip(SCAN_TABLES, offs):
+            raw = np.ascontiguousarray(self.host[name]).view(np.uint8).reshape(-1)
+            flat[o:o + raw.size] = torch.from_numpy(raw)
+        if self.device.type == 'cuda':
+            flat = flat.pin_memory()
+        self.dev = flat.to(self.device, non_blocking=True)
+        base = self.dev.data_ptr()
+        self.tab = torch.tensor([base + o for o in offs], dtype=torch.int64).to(self.device)
+
+
+class DeviceNavigator:
+    """The navigator state of B episodes of the bucket (T steps, panorama width W, map widths te.gw) over the tensors of `bufs`.
+
+        tables = ScanTables(scans, store);  nav = DeviceNavigator(te, tables, bufs, 'sample')
+        traj, actions = sp.run(episodes, rng, navigator=nav)                 # SinglePassSampledEpisode / ArgmaxEpisode
+
+    By hand: begin(episodes, rng | actions) -> for t in 0..T-1: step(t, act) then the step graph -> step(T, act) -> finish().
+    begin() is one pinned H2D copy (scan, start viewpoint and view, goal per episode; the uniforms `rng.random_sample((T, B))`, the
+    numbers the host walk draws step by step, in its order; the forced actions) next to the instruction's `txt_ids` / `txt_masks`;
+    step() launches the kernels and recomputes, into the same storage and in stream order, the memoised masks derived from the step's
+    tables (a raw kernel write does not bump a tensor's version counter); finish() is the one read-back: status words, actions, hop log
+    and n_traj.  A non-zero status word is raised there as a ValueError naming episode and step.  Nothing in between synchronises."""
+
+    def __init__(self, te, tables, bufs, mode):
+        if te.objects is not None:
+            raise NotImplementedError('DeviceNavigator: REVERIE / SOON object tables stay on the host planner (EpisodePlanner)')
+        if mode not in MODES:
+            raise ValueError('DeviceNavigator: mode is one of %s, got %r' % (sorted(MODES), mode))
+        if tables.A != te.sim.angle_feat_size:
+            raise ValueError('DeviceNavigator: the scan tables hold %d angle features, the simulator %d' % (tables.A, te.sim.angle_feat_size))
+        self.te, self.tables, self.bufs, self.mode = te, tables, bufs, mode
+        self.device = bufs.device
+        t_ = bufs.t
+        self.B, self.T, self.W, self.A = t_['txt_ids'].shape[0], te.T, te.W, tables.A
+        B, T, W = self.B, self.T, self.W
+        self.gw = [int(te.gw(t)) for t in range(T)]
+        self.cap = max(self.gw) - 2
+        if not (1 <= B <= MAX_B and 1 <= T <= MAX_T and 36 <= W <= MAX_W and 1 <= self.cap <= MAX_CAP and max(self.gw) <= MAX_G and min(self.gw) >= 2):
+            raise ValueError('DeviceNavigator: B = %d, T = %d, W = %d, map widths %d..%d outside what goat_nav_step holds (B <= %d, T <= %d, '
+                             '36 <= W <= %d, width <= %d)' % (B, T, W, min(self.gw), max(self.gw), MAX_B, MAX_T, MAX_W, min(MAX_G, MAX_CAP + 2)))
+        C = self.A + 3
+        rows = lambda t: (t + 1) * (B * W + B) + (B if t > 0 else 0)
+        self._step_tensors = []
+        ptrs = []
+        for t in range(T):
+            G, n = self.gw[t], rows(t)
+            want = {'feat_idx': (B * W,), 'feat_start': (B * W + 1,), 'loc_fts': (B, W, C), 'nav_types': (B, W), 'view_lens': (B,), 'gmap_step_ids': (B, G),
+                    'gmap_pos_fts': (B, G, C), 'gmap_pair_dists': (B, G, G), 'gmap_visited_masks': (B, G), 'gmap_masks': (B, G),
+                    'vp_pos_fts': (B, W + 2, 2 * C), 'vp_masks': (B, W + 2), 'vp_nav_masks': (B, W + 2), 'nav_fusion': (B, G, W + 2), 'target': (B,),
+                    'csr_idx': (n,), 'csr_start': (B * G + 1,), 'csr_scale': (B * G,), 'inv_idx': (n,), 'inv_start': (n + 1,), 'inv_w': (n,)}
+            ts = []
+            for name, dtype in STEP_TABLES:
+                v = t_.get('s%d_%s' % (t, name))
+                if v is None or tuple(v.shape) != want[name] or v.dtype != dtype:
+                    raise ValueError('DeviceNavigator: s%d_%s is %s, the navigator writes %s %s' % (
+                        t, name, None if v is None else (tuple(v.shape), v.dtype), want[name], dtype))
+                ts.append(v)
+            self._step_tensors.append(ts)
+            ptrs.append([v.data_ptr() for v in ts])
+        h = _lib.lib()
+        self.state_ints, self.log_ints = h.goat_nav_state_ints(T, W, self.cap), h.goat_nav_log_ints(T, self.cap)
+        if self.state_ints <= 0 or self.log_ints <= 0:
+            raise RuntimeError('libgoat_hip: goat_nav_state_ints(T=%d, W=%d, cap=%d) gave no size' % (T, W, self.cap))
+        dev = self.device
+        self.step_tab = torch.tensor(ptrs, dtype=torch.int64).to(dev)
+        self.si = torch.zeros(B * self.state_ints, dtype=torch.int32, device=dev)
+        self.sd = torch.zeros(B * (self.cap * self.cap + self.cap), dtype=torch.float64, device=dev)
+        self.log = torch.zeros(2 * T * B + B * self.log_ints, dtype=torch.int32, device=dev)
+        self._live_at = 2 * (B + 1) + T * (B * W + B) + B
+        self.ws = torch.zeros(self._live_at + 1, dtype=torch.int32, device=dev)
+        # staging of begin(): [u float64 [T, B] | ep int32 [B, 4] | forced actions int32 [T, B]]
+        self._n_u, self._n_ep = T * B * 8, B * 4 * 4
+        nbytes = self._n_u + self._n_ep + T * B * 4
+        self._stage = torch.zeros(nbytes, dtype=torch.uint8)
+        self._log_host = torch.zeros(self.log.numel(), dtype=torch.int32)
+        if dev.type == 'cuda':
+            self._stage, self._log_host = self._stage.pin_memory(), self._log_host.pin_memory()
+        self._in = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        self.u = self._in[:self._n_u].view(torch.float64).view(T, B)
+        self.ep = self._in[self._n_u:self._n_u + self._n_ep].view(torch.int32).view(B, 4)
+        self.forced = self._in[self._n_u + self._n_ep:].view(torch.int32).view(T, B)
+        self._copied = None
+        self.episodes = None
+        self.launches_per_step = 2
+
+    # ---- one walk -------------------------------------------------------------------------------------------------------------
+    def begin(self, episodes, rng=None, actions=None):
+        """start_walk for `episodes` ({instr_id, scan (ScanGraph), path, heading, instr_encoding}).  'sample': rng (numpy RandomState)
+        gives the uniforms; 'forced': actions [<= T, B] integers (missing steps are [stop], as TeacherEpisode.plan pads them)."""
+        te, B, T = self.te, self.B, self.T
+        if len(episodes) != B:
+            raise ValueError('DeviceNavigator: %d episodes for a state block of B = %d' % (len(episodes), B))
+        t0 = time.perf_counter()
+        if self._copied is not None:
+            self._copied.synchronize()              # the previous H2D has read the pinned buffer
+        st = self._stage.numpy()
+        u = st[:self._n_u].view(np.float64).reshape(T, B)
+        ep = st[self._n_u:self._n_u + self._n_ep].view(np.int32).reshape(B, 4)
+        forced = st[self._n_u + self._n_ep:].view(np.int32).reshape(T, B)
+        if self.mode == 'sample':
+            u[:] = (rng if rng is not None else np.random.RandomState(0)).random_sample((T, B))
+        forced[:] = 0
+        if self.mode == 'forced':
+            if actions is None:
+                raise ValueError('DeviceNavigator: a forced walk needs its actions')
+            acts = np.asarray([np.asarray(a, np.int64) for a in actions], np.int64).reshape(-1, B)
+            if len(acts) > T:
+                raise ValueError('%d recorded steps exceed the episode bucket T = %d' % (len(acts), T))
+            forced[:len(acts)] = acts
+        for i, e in enumerate(episodes):
+            name = e['scan'].name
+            ep[i] = (self.tables.ids[name], self.tables.vp(name, e['path'][0]), GraphSim._snap(e['heading'], 0.0), self.tables.vp(name, e['path'][-1]))
+        lang = language_inputs([{'instr_encoding': e['instr_encoding']} for e in episodes])
+        n = lang['txt_ids'].shape[1]
+        if n > te.L:
+            raise ValueError('instruction of %d tokens exceeds the text bucket %d' % (n, te.L))
+        ids = torch.zeros(B, te.L, dtype=torch.int64)
+        msk = torch.zeros(B, te.L, dtype=torch.bool)
+        ids[:, :n], msk[:, :n] = lang['txt_ids'], lang['txt_masks']
+        self.bufs.load_part({'txt_ids': ids, 'txt_masks': msk})
+        self._in.copy_(self._stage, non_blocking=True)
+        if self.device.type == 'cuda':
+            self._copied = torch.cuda.Event()
+            self._copied.record()
+        self.episodes = list(episodes)
+        self.host_s = time.perf_counter() - t0          # seconds of host work of this walk (packing here, the trajectories in finish())
+        launch('goat_nav_reset', self.tables.tab, self.si, self.sd, self.log, self.ep, B, T, self.W, self.cap,
+               what='goat_nav_reset(B=%d,T=%d,cap=%d)' % (B, T, self.cap))
+
+    def step(self, t, act=None):
+        """the move of step t - 1 decided from `act` (the step's probabilities [B, G] in 'sample' mode, the [3, B] argmax tensor of
+        the step graph in 'argmax' mode; 'forced' reads its own tensor), then the tables of step t (none at t == T)."""
+        B, T = self.B, self.T
+        if self.mode == 'forced':
+            act = self.forced
+        if t > 0 and act is None:
+            raise ValueError('DeviceNavigator.step(%d): the %s walk decides from the outputs of step %d' % (t, self.mode, t - 1))
+        launch('goat_nav_step', self.tables.tab, self.step_tab[t] if t < T else None, self.si, self.sd, self.log, self.ws,
+               act if t > 0 else None, self.u, MODES[self.mode], t, B, T, self.gw[t - 1] if t > 0 else 0, self.gw[t] if t < T else 0,
+               self.W, self.A, self.cap, int(self.te.ignoreid), what='goat_nav_step(t=%d,B=%d)' % (t, B))
+        if t < T:
+            layers.refresh_masks(only=self._step_tensors[t], force=True)
+
+    def finish(self):
+        """the read-back of the walk -> (traj, actions [steps][B], n_traj, ended [B]); raises ValueError on a status word."""
+        B, T = self.B, self.T
+        self._log_host.copy_(self.log, non_blocking=True)
+        if self.device.type == 'cuda':
+            torch.cuda.current_stream().synchronize()
+        t0 = time.perf_counter()
+        log = self._log_host.numpy()
+        acts, alive = log[:T * B].reshape(T, B), log[T * B:2 * T * B].reshape(T, B)
+        blocks = log[2 * T * B:].reshape(B, self.log_ints)
+        for i in range(B):
+            if blocks[i, H_STATUS]:
+                raise ValueError('device navigator: episode %d, step %d: %s' % (i, int(blocks[i, H_STATUS_T]), STATUS.get(int(blocks[i, H_STATUS]), 'status %d' % blocks[i, H_STATUS])))
+        names = self.tables.names
+        traj = []
+        for i, e in enumerate(self.episodes):
+            hs, hops = blocks[i, HDR:HDR + T + 2], blocks[i, HDR + T + 2:]
+            path = [[e['path'][0]]]
+            for t in range(T):
+                if hs[t + 1] > hs[t]:
+                    path.append([names[v] for v in hops[hs[t]:hs[t + 1]]])
+            if blocks[i, H_BT_N]:
+                s = int(blocks[i, H_BT_START])
+                path.append([names[v] for v in hops[s:s + int(blocks[i, H_BT_N])]])
+            traj.append({'instr_id': e['instr_id'], 'path': path})
+        actions = [acts[t].astype(np.int64) for t in range(T) if alive[t].any()]
+        self.alive = alive.astype(bool)
+        self.host_s += time.perf_counter() - t0
+        return traj, actions, int(blocks[:, H_LIVE].sum()), blocks[:, H_ENDED].astype(bool)
+
+    def walk(self, ep, episodes, rng=None, actions=None, act=None, after=None, check_every=None):
+        """the whole walk over the graphs of `ep` (g_lang, g_step): begin, per step the navigator then the step graph, the last move,
+        `after()` (the backward graph of the single pass), the read-back.  act(t): the tensor step t + 1 decides from.
+        check_every=k: before every k-th step graph the host reads the number of episodes still walking (one int; this synchronises) and
+        leaves the loop at zero, as speaker.IncrementalDecoder does — for walks that end long before T and whose later step graphs
+        nobody needs (the validation walk; not the single pass, whose backward graph differentiates through every step)."""
+        self.begin(episodes, rng, actions)
+        ep.g_lang.replay()
+        done = False
+        for t in range(self.T):
+            self.step(t, act(t - 1) if (t > 0 and act is not None) else None)
+            if check_every and t > 0 and t % check_every == 0 and int(self.ws[self._live_at].item()) == 0:
+                done = True
+                break
+            ep.g_step[t].replay()
+        if not done:
+            self.step(self.T, act(self.T - 1) if act is not None else None)
+        if after is not None:
+            after()
+        return self.finish()

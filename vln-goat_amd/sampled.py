@@ -188,11 +188,18 @@ class ArgmaxEpisode:
                 module.train(was_training)
         self.host_s, self.steps, self.actions = 0.0, 0, []
 
-    def run(self, episodes):
-        """-> the trajectories of the argmax walk, one per episode: {'instr_id', 'path', and with objects 'pred_objid'}."""
+    def run(self, episodes, navigator=None, check_every=None):
+        """-> the trajectories of the argmax walk, one per episode: {'instr_id', 'path', and with objects 'pred_objid'}.
+        navigator: a navdev.DeviceNavigator(te, tables, bufs, 'argmax') — the walk is then T navigator launches and T graph replays
+        with one read-back at its end (every step graph is replayed; an ended episode's rows stay frozen).  check_every=k: the host
+        reads the number of live episodes every k steps and stops replaying once it is zero (DeviceNavigator.walk)."""
         te, bufs = self.te, self.bufs
         if len(episodes) != self.B:
             raise ValueError('ArgmaxEpisode: %d episodes for graphs captured at B = %d' % (len(episodes), self.B))
+        if navigator is not None:
+            traj, self.actions, _, _ = navigator.walk(self, episodes, act=lambda t: self.back, check_every=check_every)
+            self.host_s, self.steps = navigator.host_s, len(self.actions)
+            return traj
         t0 = time.perf_counter()
         p = EpisodePlanner(te, episodes, imitation=False, feedback='argmax')
         self.host_s = time.perf_counter() - t0
@@ -329,10 +336,18 @@ class SinglePassSampledEpisode:
         self._pool = g.pool()
         return g, out
 
-    def run(self, episodes, rng=None, sampler=None):
+    def run(self, episodes, rng=None, sampler=None, navigator=None):
         """-> (trajectories, actions).  The parameter gradients of the sampled loss are where the model's backward puts them (the gradient
         arena / .grad) when this returns (asynchronously: on the current stream); `self.loss` is the loss of the iteration (device scalar).
-        sampler(t, probs [B, G] numpy) -> actions [B] overrides the random draw (tests: a fixed action sequence)."""
+        sampler(t, probs [B, G] numpy) -> actions [B] overrides the random draw (tests: a fixed action sequence).
+        navigator: a navdev.DeviceNavigator(te, tables, bufs, 'sample') — the walk is decided on the device from the same uniforms
+        (`rng.random_sample((T, B))`), with no read-back before the backward graph has been launched; returns after the one read-back."""
+        if navigator is not None:
+            if sampler is not None:
+                raise ValueError('SinglePassSampledEpisode: a sampler decides on the host; the device navigator samples itself')
+            traj, actions, self.n_traj, _ = navigator.walk(self, episodes, rng=rng, act=lambda t: self.probs[t], after=self.g_bwd.replay)
+            self.host_s, self.steps = navigator.host_s, len(actions)
+            return traj, actions
         p, actions = _sampled_walk(self, episodes, rng, sampler, replay_all=True)
         self.g_bwd.replay()
         self.n_traj = p.n_traj
