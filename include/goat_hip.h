@@ -692,6 +692,28 @@ int goat_nav_step(void* stream, const int64_t* scan_tab, const int64_t* step_tab
                   const void* act, const double* u, int mode, int t, int B, int T, int G_prev, int G, int W, int A, int cap,
                   int64_t ignoreid);
 
+/* goat_nav_ndtw: the DAgger label of the nDTW expert (csrc/navexpert_core.hpp) for step t < T, launched behind goat_nav_step(t) on the
+ * same state: `_teacher_action` under expert_policy = 'ndtw' (M/r2r/agent.py:330-346, what the RxR scripts set) with `cal_dtw`
+ * (M/r2r/eval_utils.py:6-26).  Per selectable unvisited map slot g >= 2 the DTW between (walked path + shortest path from the current
+ * viewpoint to the slot's node) and the episode's ground-truth path; the first slot whose DTW is strictly smallest is written to the
+ * step's `target` over the shortest-path label goat_nav_step put there (ignoreid for an ended episode or without a candidate, 0 on the
+ * goal).  The kernel orders by DTW, not by -nDTW = -exp(-DTW / (3 R)): exp is monotone, so the two agree except where rounding maps two
+ * DTWs to one double.  Every cell is cost + min(up, left, diag) in float64 in cal_dtw's order, rows filled serially (no scan across
+ * lanes), so the labels equal nav_inputs.teacher_action(expert_policy='ndtw') exactly.
+ *   scan_tab   as goat_nav_step, with a 15th address: the predecessor matrices int32 of the scans' all-pairs shortest paths
+ *              (ScanGraph.shortest()[1], scan-local indices) at the offsets of the distances.  goat_nav_step reads the first 14 only.
+ *   ref        int32 [B, max_ref + 1]: the length R of an episode's ground-truth path (1 <= R <= max_ref), then its viewpoint numbers.
+ *   xd         float64, B blocks of goat_nav_expert_doubles(cap, max_ref): the DTW row behind the last folded node of the walked path and
+ *              one working row per map node.  The fold counter is header word 21 of the episode's log block, cleared by goat_nav_reset.
+ * One workgroup of 256 threads per episode; the walked path is folded forward by the hops logged since the last call (thread 0), then
+ * one thread per candidate.  A predecessor chain that does not reach the current viewpoint sets status word 4.
+ * GOAT_E_ARG: a null pointer; GOAT_E_SHAPE: B, T, W, cap outside the limits above, max_ref < 1 or > GOAT_NAV_MAX_REF, t outside [0, T).
+ * Both are returned before any launch.  goat_nav_expert_doubles is a value (0 for sizes outside the limits). */
+#define GOAT_NAV_MAX_REF 64
+int goat_nav_expert_doubles(int cap, int max_ref);
+int goat_nav_ndtw(void* stream, const int64_t* scan_tab, const int64_t* step_tab, int32_t* si, double* sd, int32_t* log,
+                  const int32_t* ref, double* xd, int t, int B, int T, int W, int cap, int max_ref, int64_t ignoreid);
+
 #ifdef __cplusplus
 }
 #endif

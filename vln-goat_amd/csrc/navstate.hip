@@ -16,12 +16,15 @@
 // serial parts are chains of dependent loads over them, each a fraction of a trip to L2 when it comes from LDS.  Every value
 // that must equal the host's bit for bit is one IEEE operation with contraction off.  A second launch of ONE workgroup forms the
 // batch-wide compact CSRs (prefix sums over the episodes, fixed order, no atomics).
+// goat_nav_ndtw is a third, optional launch behind the two: the DAgger label of the nDTW expert (csrc/navexpert_core.hpp) over the
+// step kernel's shortest-path label, for walks whose TeacherEpisode has expert_policy = 'ndtw'.
 // Errors (a map wider than the bucket, a panorama wider than W, an action that is no selectable node) become a sticky status word
 // per episode; the kernel clamps and goes on.
 #include "common.hpp"
 
 #define NAV_HD __host__ __device__
 #include "navstate_core.hpp"
+#include "navexpert_core.hpp"
 
 namespace {
 
@@ -44,6 +47,14 @@ __global__ __launch_bounds__(256) void nav_step_kernel(Args a) {
 __global__ __launch_bounds__(256) void nav_tail_kernel(Args a) {
   __shared__ int32_t part[256];
   nav_tail(a, part, threadIdx.x, blockDim.x, DevSync());
+}
+
+// goat_nav_ndtw (the comment of csrc/navexpert_core.hpp says what it restates): one workgroup per episode behind the step kernel.  The
+// ground-truth path and the shared DTW row are staged in LDS for the serial fold; the candidates' rows stay in HBM / L2.
+__global__ __launch_bounds__(256) void nav_ndtw_kernel(Args a, Expert x) {
+  __shared__ double row_s[GOAT_NAV_MAX_REF + 1];
+  __shared__ int32_t ref_s[GOAT_NAV_MAX_REF + 1];
+  ndtw_label(a, x, blockIdx.x, threadIdx.x, blockDim.x, DevSync(), row_s, ref_s);
 }
 
 int nav_sizes_bad(int B, int T, int W, int cap) {
@@ -91,5 +102,31 @@ extern "C" int goat_nav_step(void* stream, const int64_t* scan_tab, const int64_
     hipLaunchKernelGGL(nav_tail_kernel, dim3(1), dim3(256), 0, ST(stream), a);
     GOAT_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+extern "C" int goat_nav_expert_doubles(int cap, int max_ref) {
+  return (nav_sizes_bad(1, 1, 1, cap) || max_ref < 1 || max_ref > GOAT_NAV_MAX_REF) ? 0 : expert_doubles(cap, max_ref);
+}
+
+extern "C" int goat_nav_ndtw(void* stream, const int64_t* scan_tab, const int64_t* step_tab, int32_t* si, double* sd, int32_t* log,
+                             const int32_t* ref, double* xd, int t, int B, int T, int W, int cap, int max_ref, int64_t ignoreid) {
+  if (!scan_tab || !step_tab || !si || !sd || !log || !ref || !xd) return GOAT_E_ARG;
+  if (nav_sizes_bad(B, T, W, cap) || max_ref < 1 || max_ref > GOAT_NAV_MAX_REF || t < 0 || t >= T) return GOAT_E_SHAPE;
+  Args a = {};
+  a.scan_tab = scan_tab;
+  a.step_tab = step_tab;
+  a.si = si;
+  a.sd = sd;
+  a.log = log;
+  a.t = t;
+  a.B = B;
+  a.T = T;
+  a.W = W;
+  a.cap = cap;
+  a.ignoreid = ignoreid;
+  const Expert x = {ref, xd, max_ref};
+  hipLaunchKernelGGL(nav_ndtw_kernel, dim3(B), dim3(256), 0, ST(stream), a, x);
+  GOAT_LAUNCH_CHECK();
   return 0;
 }

@@ -16,13 +16,13 @@ constexpr double NAV_INF = 95959595.0;      // graph_utils.py:45
 constexpr int HDR = 32;
 // header words of an episode (the first HDR ints of its read-back block)
 enum { H_CUR = 0, H_VIEW, H_ENDED, H_JUST, H_N, H_STATUS, H_STATUS_T, H_START, H_GOAL, H_NOLEFT, H_NSCORED, H_LIVE, H_NSLOT, H_VLEN,
-       H_NCAND, H_STARTVIEW, H_HOPN, H_BT_START, H_BT_N, H_K, H_SCAN };
+       H_NCAND, H_STARTVIEW, H_HOPN, H_BT_START, H_BT_N, H_K, H_SCAN, H_FOLD /* navexpert_core.hpp: 1 + the hops folded into its DTW row */ };
 enum { ST_OK = 0, ST_MAP = 1, ST_PANO = 2, ST_ACTION = 3, ST_PATH = 4 };
 enum { MODE_SAMPLE = 0, MODE_ARGMAX = 1, MODE_FORCED = 2 };
 enum { KIND_NONE = 0, KIND_SET = 1, KIND_ACC = 2 };
 // the static scan tables, in the order of the address table `scan_tab`
 enum { SC_POS = 0, SC_CAND_START, SC_CAND_NB, SC_CAND_POINT, SC_CAND_ANG, SC_CAND_LEN, SC_FEATURE_ROW, SC_VP_SCAN, SC_SCAN_OFF, SC_SCAN_N,
-       SC_DIST_OFF, SC_DIST, SC_VAF, SC_VIEW_ANG, SC_COUNT };
+       SC_DIST_OFF, SC_DIST, SC_VAF, SC_VIEW_ANG, SC_PRED /* read by navexpert_core.hpp only */, SC_COUNT };
 // the tables of one step, in the order of the address table `step_tab`
 enum { TB_FEAT_IDX = 0, TB_FEAT_START, TB_LOC_FTS, TB_NAV_TYPES, TB_VIEW_LENS, TB_STEP_IDS, TB_GMAP_POS, TB_PAIR, TB_VISITED, TB_GMASK,
        TB_VP_POS, TB_VP_MASK, TB_VP_NAV, TB_FUSION, TB_TARGET, TB_CSR_IDX, TB_CSR_START, TB_CSR_SCALE, TB_INV_IDX, TB_INV_START, TB_INV_W,

@@ -18,8 +18,8 @@ import torch
 
 from . import hipops, layers
 from .navsim import GraphSim
-from .nav_inputs import (language_inputs, panorama_inputs, gmap_inputs, vp_inputs, teacher_object, teacher_action, start_walk,
-                         note_step, nodefault, fused_or_mean, pick_logits)
+from .nav_inputs import (EXPERT_POLICIES, language_inputs, panorama_inputs, gmap_inputs, vp_inputs, teacher_object, teacher_action,
+                         start_walk, note_step, nodefault, fused_or_mean, pick_logits)
 
 
 # ------------------------------------------------------------------------------------------------ teacher-forced episodes as ONE graph
@@ -39,7 +39,7 @@ class TeacherEpisode:
     plan's step count carry target -100 (ignored) after their end, as the reference's `ended` bookkeeping does."""
 
     def __init__(self, sim, features, n_steps, text_len, pano_width=40, gmap_width=default_gmap_width, fusion='dynamic', ignoreid=-100,
-                 obj_width=20):
+                 obj_width=20, expert_policy='spl'):
         self.sim, self.features = sim, features
         self.T, self.L, self.W, self.gw = n_steps, text_len, pano_width, gmap_width
         self.fusion, self.ignoreid = fusion, ignoreid
@@ -48,6 +48,13 @@ class TeacherEpisode:
         self.objects = getattr(sim, 'objects', None)
         self.O = obj_width if self.objects is not None else 0
         self.WT = self.W + self.O
+        # the DAgger expert of the states a sampled walk visits (plan(actions=), EpisodePlanner(imitation=False)): 'spl', or 'ndtw' as the
+        # RxR scripts set it (M/r2r/agent.py:330-346).  The REVERIE agent has the shortest-path expert only (M/reverie/agent_obj_goat.py:390-417).
+        if expert_policy not in EXPERT_POLICIES:
+            raise ValueError('TeacherEpisode: expert_policy is one of %s, got %r' % (EXPERT_POLICIES, expert_policy))
+        if expert_policy == 'ndtw' and self.objects is not None:
+            raise ValueError('TeacherEpisode: the REVERIE / SOON agent has the shortest-path expert only; expert_policy=\'ndtw\' needs a walk without objects')
+        self.expert_policy = expert_policy
 
     # ---- host ---------------------------------------------------------------------------------------------------------------
     def plan(self, episodes, actions=None):
@@ -260,7 +267,8 @@ class EpisodePlanner:
         vin = vp_inputs(obs, gmaps, pano['cand_vpids'], pano['view_lens'], pano['nav_types'], te.WT + 2, afs,
                         gmap_pos=(gin['gmap_vpids'], gin['gmap_pos_fts'].numpy()), obj_lens=pano['reverie_obj_lens'] if has_obj else None)
         # (the REVERIE agent has the shortest-path expert only, M/reverie/agent_obj_goat.py:390-417)
-        target = teacher_action(obs, gin['gmap_vpids'], ended, gin['gmap_visited_masks'].numpy(), self.imitation and not has_obj, t, te.ignoreid)
+        target = teacher_action(obs, gin['gmap_vpids'], ended, gin['gmap_visited_masks'].numpy(), self.imitation and not has_obj, t, te.ignoreid,
+                                expert_policy=te.expert_policy, traj=self.traj)
         k = 's%d_' % t
         # feature gather of the panorama tokens: compact CSR (padding slots = empty segments)
         out[k + 'feat_idx'], out[k + 'feat_start'] = _compact_rows(pano['view_rows'])
@@ -391,7 +399,8 @@ def _plan_worker_main(conn, spec):
     scans = spec['scans']
     te = TeacherEpisode(GraphSim(_RowIndex(spec['keys']), spec['angle_feat_size'], objects=spec.get('objects')), None, spec['n_steps'],
                         spec['text_len'], pano_width=spec['pano_width'], gmap_width=lambda t, w=spec['gmap_widths']: w[min(t, len(w) - 1)],
-                        fusion=spec['fusion'], ignoreid=spec['ignoreid'], obj_width=spec.get('obj_width', 20))
+                        fusion=spec['fusion'], ignoreid=spec['ignoreid'], obj_width=spec.get('obj_width', 20),
+                        expert_policy=spec.get('expert_policy', 'spl'))
     while True:
         try:
             episodes = conn.recv()
@@ -428,7 +437,7 @@ class PlanWorker:
         scans = {sc.name: sc for sc in (scans.values() if isinstance(scans, dict) else scans)}
         spec = {'keys': list(keys), 'scans': scans, 'angle_feat_size': te.sim.angle_feat_size, 'n_steps': te.T, 'text_len': te.L,
                 'pano_width': te.W, 'gmap_widths': [int(te.gw(t)) for t in range(max(te.T, 1))], 'fusion': te.fusion, 'ignoreid': te.ignoreid,
-                'objects': te.objects.meta() if te.objects is not None else None, 'obj_width': te.O}      # (REVERIE: object metadata, no features)
+                'objects': te.objects.meta() if te.objects is not None else None, 'obj_width': te.O, 'expert_policy': te.expert_policy}      # (REVERIE: object metadata, no features)
         self.proc = ctx.Process(target=_plan_worker_main, args=(child, spec), daemon=True)
         self.proc.start()
         child.close()

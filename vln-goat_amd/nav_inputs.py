@@ -186,8 +186,32 @@ def teacher_object(obs, ended, view_lens, ignoreid=-100):
     return t
 
 
-def teacher_action(obs, vpids, ended, visited_masks=None, imitation_learning=False, t=None, ignoreid=-100):
-    """_teacher_action (M/r2r/agent.py:306-347), expert policy 'spl'."""
+EXPERT_POLICIES = ('spl', 'ndtw')
+
+
+def cal_dtw(dist, prediction, reference, threshold=3.0):
+    """cal_dtw (M/r2r/eval_utils.py:6-26) over a dense distance matrix: prediction / reference are rows / columns of `dist` (indices of
+    `ScanGraph.vpids`).  The loops, their order and the float64 operations are the reference's; -> {'DTW', 'nDTW'}."""
+    dtw_matrix = np.inf * np.ones((len(prediction) + 1, len(reference) + 1))
+    dtw_matrix[0][0] = 0
+    for i in range(1, len(prediction) + 1):
+        for j in range(1, len(reference) + 1):
+            best_previous_cost = min(dtw_matrix[i - 1][j], dtw_matrix[i][j - 1], dtw_matrix[i - 1][j - 1])
+            cost = dist[prediction[i - 1]][reference[j - 1]]
+            dtw_matrix[i][j] = cost + best_previous_cost
+    dtw = dtw_matrix[len(prediction)][len(reference)]
+    return {'DTW': dtw, 'nDTW': np.exp(-dtw / (threshold * len(reference)))}
+
+
+def teacher_action(obs, vpids, ended, visited_masks=None, imitation_learning=False, t=None, ignoreid=-100, expert_policy='spl', traj=None):
+    """_teacher_action (M/r2r/agent.py:306-347).  expert_policy (imitation_learning=False): 'spl', the unvisited node with the shortest
+    way to the goal through it, or 'ndtw' (:330-346, the RxR scripts), the unvisited node whose shortest path from the current
+    viewpoint, appended to the walked path `traj[i]['path']`, keeps the highest nDTW to the ground-truth path.  Shortest paths are
+    `ScanGraph.shortest_path` (the reference takes networkx's)."""
+    if expert_policy not in EXPERT_POLICIES:
+        raise ValueError('teacher_action: expert_policy is one of %s, got %r' % (EXPERT_POLICIES, expert_policy))
+    if expert_policy == 'ndtw' and not imitation_learning and traj is None:
+        raise ValueError('teacher_action: the ndtw expert scores the walked path: pass traj')
     a = np.zeros(len(obs), dtype=np.int64)
     for i, ob in enumerate(obs):
         if ended[i]:
@@ -209,10 +233,17 @@ def teacher_action(obs, vpids, ended, visited_masks=None, imitation_learning=Fal
             dist, _ = scan.shortest()
             cur, goal = scan.index[ob['viewpoint']], scan.index[ob['gt_path'][-1]]
             best, best_d = ignoreid, float('inf')
+            if expert_policy == 'ndtw':
+                walked = [scan.index[vp] for vp in sum(traj[i]['path'], [])]
+                gt = [scan.index[vp] for vp in ob['gt_path']]
             for j, vpid in enumerate(vpids[i]):
                 if j > 1 and ((visited_masks is None) or (not visited_masks[i][j])):
                     k = scan.index[vpid]
-                    d = dist[k, goal] + dist[cur, k]
+                    if expert_policy == 'ndtw':
+                        there = [scan.index[vp] for vp in scan.shortest_path(ob['viewpoint'], vpid)[1:]]
+                        d = -cal_dtw(dist, walked + there, gt, threshold=3.0)['nDTW']
+                    else:
+                        d = dist[k, goal] + dist[cur, k]
                     if d < best_d:
                         best_d, best = d, j
             a[i] = best

@@ -7,13 +7,18 @@ the navigator's state lives in HBM and `goat_nav_step` does advance() + build_st
 the addresses the captured step graph reads: the walk is one loop of launches, without a device -> host copy or a synchronisation
 before its end.  The host planner stays as it is and is the reference this module is tested against.
 
-  * `ScanTables`        the static tables of a set of ScanGraphs (positions, candidate lists, edge lengths, shortest distances,
-                        feature rows, the view-angle table), built and uploaded once; `.host` holds them as numpy arrays.
+  * `ScanTables`        the static tables of a set of ScanGraphs (positions, candidate lists, edge lengths, shortest distances and
+                        their predecessor matrices, feature rows, the view-angle table), built and uploaded once; `.host` holds them
+                        as numpy arrays.
   * `DeviceNavigator`   the per-episode state block of one (B, T) bucket over an `EpisodeBuffers`, in one of three modes: 'sample'
                         (SampledEpisode.sample restated on the device), 'argmax' (the stop rule, stop scores and backtrack of the
                         validation walk) and 'forced' (a given [T, B] action tensor: TeacherEpisode.plan(actions=...)).
 
-Scope: R2R-style walks.  The REVERIE / SOON object tables (`te.objects`) stay on the host planner, and so does the two-pass
+The DAgger labels follow `te.expert_policy`: 'spl' comes out of `goat_nav_step` itself; with 'ndtw' (the RxR scripts) a third launch per
+step, `goat_nav_ndtw` (csrc/navexpert_core.hpp), writes the nDTW expert's label over it from the walked path it folds forward on the
+device and the episode's ground-truth path, staged by begin() in a bucket of `max_ref` viewpoints.
+
+Scope: R2R- and RxR-style walks.  The REVERIE / SOON object tables (`te.objects`) stay on the host planner, and so does the two-pass
 `SampledEpisode`, which needs finish()'s joined `all_*` tables and is the slower form of the sampled half anyway."""
 import time
 
@@ -22,7 +27,7 @@ import torch
 
 from . import _lib, layers
 from ._plumbing import launch
-from .nav_inputs import language_inputs
+from .nav_inputs import EXPERT_POLICIES, language_inputs
 from .navsim import GraphSim, view_angle_feature_table, view_angles
 
 MODES = {'sample': 0, 'argmax': 1, 'forced': 2}
@@ -30,7 +35,7 @@ STATUS = {1: 'the map has more nodes than the bucket of the step holds', 2: 'the
           3: 'the action is not a selectable node of the map', 4: 'the hop log or a path stack overflowed'}
 # the order of the address tables (csrc/navstate_core.hpp)
 SCAN_TABLES = ('pos', 'cand_start', 'cand_nb', 'cand_point', 'cand_ang', 'cand_len', 'feature_row', 'vp_scan', 'scan_off', 'scan_n',
-               'dist_off', 'dist', 'vaf', 'view_ang')
+               'dist_off', 'dist', 'vaf', 'view_ang', 'pred')
 STEP_TABLES = (('feat_idx', torch.int32), ('feat_start', torch.int32), ('loc_fts', torch.float32), ('nav_types', torch.int64),
                ('view_lens', torch.int64), ('gmap_step_ids', torch.int64), ('gmap_pos_fts', torch.float32), ('gmap_pair_dists', torch.float32),
                ('gmap_visited_masks', torch.bool), ('gmap_masks', torch.bool), ('vp_pos_fts', torch.float32), ('vp_masks', torch.bool),
@@ -38,14 +43,15 @@ STEP_TABLES = (('feat_idx', torch.int32), ('feat_start', torch.int32), ('loc_fts
                ('csr_start', torch.int32), ('csr_scale', torch.float32), ('inv_idx', torch.int32), ('inv_start', torch.int32),
                ('inv_w', torch.float32))
 H_ENDED, H_STATUS, H_STATUS_T, H_LIVE, H_HOPN, H_BT_START, H_BT_N, HDR = 2, 5, 6, 11, 16, 17, 18, 32
-MAX_B, MAX_T, MAX_G, MAX_W, MAX_CAP = 1024, 64, 256, 64, 254        # GOAT_NAV_MAX_* (include/goat_hip.h)
+MAX_B, MAX_T, MAX_G, MAX_W, MAX_CAP, MAX_REF = 1024, 64, 256, 64, 254, 64        # GOAT_NAV_MAX_* (include/goat_hip.h)
 
 
 class ScanTables:
     """The read-only tables `goat_nav_step` walks on, for the ScanGraphs `scans`.  Viewpoints are numbered across the scans
     (`first[scan name]` + the scan's own index); per viewpoint: position, the candidate list in the order of `ScanGraph.candidates(vp)`
     (neighbour, pointId, normalized heading / elevation, and the edge length exactly as `GraphMap.update_graph` computes it) and the
-    feature row; per scan: the all-pairs distances of `ScanGraph.shortest()`.  row_of: `row(scan_name, vp) -> int` or an object with that
+    feature row; per scan: the all-pairs distances of `ScanGraph.shortest()` and, at the same offsets, its predecessor matrix (`pred`,
+    int32, scan-local indices: `pred[i, j]` comes before j on the shortest path from i).  row_of: `row(scan_name, vp) -> int` or an object with that
     method (features.FeatureStore).  device=None keeps the tables on the host only (`.host`: {name: numpy array})."""
 
     def __init__(self, scans, row_of, angle_feat_size=4, device='cuda'):
@@ -57,7 +63,7 @@ class ScanTables:
         for sc in scans:
             self.first[sc.name] = len(self.names)
             self.names += list(sc.vpids)
-        pos, cstart, cnb, cpt, cang, clen, frow, vscan, dist, doff = [], [0], [], [], [], [], [], [], [], [0]
+        pos, cstart, cnb, cpt, cang, clen, frow, vscan, dist, doff, pred = [], [0], [], [], [], [], [], [], [], [0], []
         for k, sc in enumerate(scans):
             off = self.first[sc.name]
             for vp in sc.vpids:
@@ -73,6 +79,7 @@ class ScanTables:
                 vscan.append(k)
             pos.append(sc.pos)
             dist.append(np.asarray(sc.shortest()[0], np.float64).reshape(-1))
+            pred.append(np.asarray(sc.shortest()[1], np.int32).reshape(-1))
             doff.append(doff[-1] + dist[-1].size)
         self.host = {
             'pos': np.concatenate(pos, 0).astype(np.float64), 'cand_start': np.asarray(cstart, np.int32), 'cand_nb': np.asarray(cnb, np.int32),
@@ -80,7 +87,7 @@ class ScanTables:
             'feature_row': np.asarray(frow, np.int32), 'vp_scan': np.asarray(vscan, np.int32),
             'scan_off': np.asarray([self.first[sc.name] for sc in scans], np.int32), 'scan_n': np.asarray([len(sc.vpids) for sc in scans], np.int32),
             'dist_off': np.asarray(doff[:-1], np.int64), 'dist': np.concatenate(dist), 'vaf': view_angle_feature_table(angle_feat_size),
-            'view_ang': np.asarray([view_angles(v) for v in range(36)], np.float64)}
+            'view_ang': np.asarray([view_angles(v) for v in range(36)], np.float64), 'pred': np.concatenate(pred)}
         self.device = None if device is None else torch.device(device)
         self.dev, self.tab = None, None
         if self.device is not None:
@@ -92,7 +99,7 @@ class ScanTables:
         return self.first[scan_name] + sc.index[vpid]
 
     def _upload(self):
-        """one packed buffer, one H2D copy; `tab` = the addresses of the tables inside it (device int64 [14])"""
+        """one packed buffer, one H2D copy; `tab` = the addresses of the tables inside it (device int64 [15])"""
         offs, n = [], 0
         for name in SCAN_TABLES:
             offs.append(n)
@@ -115,17 +122,25 @@ class DeviceNavigator:
         traj, actions = sp.run(episodes, rng, navigator=nav)                 # SinglePassSampledEpisode / ArgmaxEpisode
 
     By hand: begin(episodes, rng | actions) -> for t in 0..T-1: step(t, act) then the step graph -> step(T, act) -> finish().
+    max_ref (te.expert_policy = 'ndtw' only): the bucket of the ground-truth path in viewpoints, at most 64; begin() raises ValueError
+    for a longer path, before any launch.
     begin() is one pinned H2D copy (scan, start viewpoint and view, goal per episode; the uniforms `rng.random_sample((T, B))`, the
-    numbers the host walk draws step by step, in its order; the forced actions) next to the instruction's `txt_ids` / `txt_masks`;
+    numbers the host walk draws step by step, in its order; the forced actions; the ground-truth paths for the nDTW expert) next to the instruction's `txt_ids` / `txt_masks`;
     step() launches the kernels and recomputes, into the same storage and in stream order, the memoised masks derived from the step's
     tables (a raw kernel write does not bump a tensor's version counter); finish() is the one read-back: status words, actions, hop log
     and n_traj.  A non-zero status word is raised there as a ValueError naming episode and step.  Nothing in between synchronises."""
 
-    def __init__(self, te, tables, bufs, mode):
+    def __init__(self, te, tables, bufs, mode, max_ref=32):
         if te.objects is not None:
             raise NotImplementedError('DeviceNavigator: REVERIE / SOON object tables stay on the host planner (EpisodePlanner)')
         if mode not in MODES:
             raise ValueError('DeviceNavigator: mode is one of %s, got %r' % (sorted(MODES), mode))
+        self.expert = getattr(te, 'expert_policy', 'spl')
+        if self.expert not in EXPERT_POLICIES:
+            raise ValueError('DeviceNavigator: expert_policy is one of %s, got %r' % (EXPERT_POLICIES, self.expert))
+        if self.expert == 'ndtw' and not 1 <= max_ref <= MAX_REF:
+            raise ValueError('DeviceNavigator: max_ref = %d outside what goat_nav_ndtw holds (1..%d)' % (max_ref, MAX_REF))
+        self.max_ref = max_ref
         if tables.A != te.sim.angle_feat_size:
             raise ValueError('DeviceNavigator: the scan tables hold %d angle features, the simulator %d' % (tables.A, te.sim.angle_feat_size))
         self.te, self.tables, self.bufs, self.mode = te, tables, bufs, mode
@@ -168,9 +183,12 @@ class DeviceNavigator:
         self.log = torch.zeros(2 * T * B + B * self.log_ints, dtype=torch.int32, device=dev)
         self._live_at = 2 * (B + 1) + T * (B * W + B) + B
         self.ws = torch.zeros(self._live_at + 1, dtype=torch.int32, device=dev)
-        # staging of begin(): [u float64 [T, B] | ep int32 [B, 4] | forced actions int32 [T, B]]
+        # staging of begin(): [u float64 [T, B] | ep int32 [B, 4] | forced actions int32 [T, B]] and, for the nDTW expert, behind them
+        # [ground-truth paths int32 [B, max_ref + 1]: length, viewpoint numbers]
         self._n_u, self._n_ep = T * B * 8, B * 4 * 4
-        nbytes = self._n_u + self._n_ep + T * B * 4
+        self._n_forced = T * B * 4
+        ndtw = self.expert == 'ndtw'
+        nbytes = self._n_u + self._n_ep + self._n_forced + (B * (max_ref + 1) * 4 if ndtw else 0)
         self._stage = torch.zeros(nbytes, dtype=torch.uint8)
         self._log_host = torch.zeros(self.log.numel(), dtype=torch.int32)
         if dev.type == 'cuda':
@@ -178,10 +196,19 @@ class DeviceNavigator:
         self._in = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.u = self._in[:self._n_u].view(torch.float64).view(T, B)
         self.ep = self._in[self._n_u:self._n_u + self._n_ep].view(torch.int32).view(B, 4)
-        self.forced = self._in[self._n_u + self._n_ep:].view(torch.int32).view(T, B)
+        self.forced = self._in[self._n_u + self._n_ep:self._n_u + self._n_ep + self._n_forced].view(torch.int32).view(T, B)
         self._copied = None
         self.episodes = None
         self.launches_per_step = 2
+        if ndtw:
+            # the DTW row of the walked path and one working row per map node: sized by this navigator's cap and max_ref, not by the
+            # limits of the ABI (there: 133 KB per episode)
+            self.expert_doubles = h.goat_nav_expert_doubles(self.cap, max_ref)
+            if self.expert_doubles <= 0:
+                raise RuntimeError('libgoat_hip: goat_nav_expert_doubles(cap=%d, max_ref=%d) gave no size' % (self.cap, max_ref))
+            self.ref = self._in[self._n_u + self._n_ep + self._n_forced:].view(torch.int32).view(B, max_ref + 1)
+            self.xd = torch.zeros(B * self.expert_doubles, dtype=torch.float64, device=dev)
+            self.launches_per_step = 3
 
     # ---- one walk -------------------------------------------------------------------------------------------------------------
     def begin(self, episodes, rng=None, actions=None):
@@ -196,7 +223,7 @@ class DeviceNavigator:
         st = self._stage.numpy()
         u = st[:self._n_u].view(np.float64).reshape(T, B)
         ep = st[self._n_u:self._n_u + self._n_ep].view(np.int32).reshape(B, 4)
-        forced = st[self._n_u + self._n_ep:].view(np.int32).reshape(T, B)
+        forced = st[self._n_u + self._n_ep:self._n_u + self._n_ep + self._n_forced].view(np.int32).reshape(T, B)
         if self.mode == 'sample':
             u[:] = (rng if rng is not None else np.random.RandomState(0)).random_sample((T, B))
         forced[:] = 0
@@ -207,6 +234,16 @@ class DeviceNavigator:
             if len(acts) > T:
                 raise ValueError('%d recorded steps exceed the episode bucket T = %d' % (len(acts), T))
             forced[:len(acts)] = acts
+        if self.expert == 'ndtw':
+            ref = st[self._n_u + self._n_ep + self._n_forced:].view(np.int32).reshape(B, self.max_ref + 1)
+            for i, e in enumerate(episodes):
+                if not 1 <= len(e['path']) <= self.max_ref:
+                    raise ValueError('DeviceNavigator: the ground-truth path of episode %d has %d viewpoints, the bucket max_ref holds 1..%d'
+                                     % (i, len(e['path']), self.max_ref))
+            ref[:] = 0
+            for i, e in enumerate(episodes):
+                ref[i, 0] = len(e['path'])
+                ref[i, 1:1 + len(e['path'])] = [self.tables.vp(e['scan'].name, vp) for vp in e['path']]
         for i, e in enumerate(episodes):
             name = e['scan'].name
             ep[i] = (self.tables.ids[name], self.tables.vp(name, e['path'][0]), GraphSim._snap(e['heading'], 0.0), self.tables.vp(name, e['path'][-1]))
@@ -238,6 +275,9 @@ class DeviceNavigator:
         launch('goat_nav_step', self.tables.tab, self.step_tab[t] if t < T else None, self.si, self.sd, self.log, self.ws,
                act if t > 0 else None, self.u, MODES[self.mode], t, B, T, self.gw[t - 1] if t > 0 else 0, self.gw[t] if t < T else 0,
                self.W, self.A, self.cap, int(self.te.ignoreid), what='goat_nav_step(t=%d,B=%d)' % (t, B))
+        if t < T and self.expert == 'ndtw':
+            launch('goat_nav_ndtw', self.tables.tab, self.step_tab[t], self.si, self.sd, self.log, self.ref, self.xd, t, B, T, self.W, self.cap,
+                   self.max_ref, int(self.te.ignoreid), what='goat_nav_ndtw(t=%d,B=%d)' % (t, B))
         if t < T:
             layers.refresh_masks(only=self._step_tensors[t], force=True)
 

@@ -28,7 +28,7 @@ import torch
 
 from .navsim import (MAX_DIST, MAX_STEP, FLOYD_INF, HFOV, VFOV, angle_feature, get_angle_fts, view_angles,  # noqa: F401
                      view_angle_feature_table, rel_pos, FloydGraph, GraphMap, NodeEmbedStore, ScanGraph, ObjectStore, GraphSim)
-from .nav_inputs import (language_inputs, panorama_inputs, panorama_object_inputs, gmap_order, gmap_inputs, vp_inputs,  # noqa: F401
+from .nav_inputs import (EXPERT_POLICIES, cal_dtw, language_inputs, panorama_inputs, panorama_object_inputs, gmap_order, gmap_inputs, vp_inputs,  # noqa: F401
                          teacher_object, teacher_action, start_walk, note_step, nodefault, fused_or_mean, pick_logits)
 from .episodes import (default_gmap_width, TeacherEpisode, _obj_concat_tables, EpisodePlanner, _RowIndex, _plan_worker_main,  # noqa: F401
                        PlanWorker, _pad1np, EpisodeBuffers)
@@ -48,8 +48,13 @@ class NavRollout:
     bucket (shape-stable steps: a captured step graph per bucket can be replayed; None = the reference's per-batch maxima)."""
 
     def __init__(self, model, sim, features, max_action_len=15, fusion='dynamic', ignoreid=-100, pano_width=None, gmap_buckets=None,
-                 device='cuda', hoist_text_kv=True, obj_width=None, teacher_scores=True):
+                 device='cuda', hoist_text_kv=True, obj_width=None, teacher_scores=True, expert_policy='spl'):
         self.model, self.sim, self.features = model, sim, features
+        if expert_policy not in EXPERT_POLICIES:
+            raise ValueError('NavRollout: expert_policy is one of %s, got %r' % (EXPERT_POLICIES, expert_policy))
+        if expert_policy == 'ndtw' and getattr(sim, 'objects', None) is not None:
+            raise ValueError('NavRollout: the REVERIE / SOON agent has the shortest-path expert only; expert_policy=\'ndtw\' needs a walk without objects')
+        self.expert_policy = expert_policy      # the DAgger expert of feedback != 'teacher' (M/r2r/agent.py:330-346; 'ndtw' in the RxR scripts)
         self.teacher_scores = teacher_scores    # teacher forcing records stop scores / best objects too, as the reference (one read-back per step)
         self.objects = getattr(sim, 'objects', None)      # REVERIE / SOON: object tokens + object grounding (M/reverie/agent_obj_goat.py:560-790)
         self.obj_width = obj_width
@@ -119,7 +124,8 @@ class NavRollout:
             target = None
             if compute_loss or feedback == 'teacher':
                 target = teacher_action(obs, nav_vpids, ended, visited_masks=gin['gmap_visited_masks'].numpy() if self.fusion != 'local' else None,
-                                        imitation_learning=(feedback == 'teacher' and not has_obj), t=t, ignoreid=self.ignoreid)      # (the REVERIE agent has the shortest-path expert only, M/reverie/agent_obj_goat.py:390-417)
+                                        imitation_learning=(feedback == 'teacher' and not has_obj), t=t, ignoreid=self.ignoreid,
+                                        expert_policy=self.expert_policy, traj=traj)      # (the REVERIE agent has the shortest-path expert only, M/reverie/agent_obj_goat.py:390-417)
             self.host_s += time.perf_counter() - t_host
             zero = pano_embeds.new_zeros(B, 1, pano_embeds.shape[-1])
             memtok = zero if last_embeds is None else last_embeds.unsqueeze(1).to(pano_embeds.dtype)

@@ -481,6 +481,21 @@ def rollout_episodes(scan, rs, B=3, max_steps=5, starts=None):
     return eps
 
 
+def rxr_episodes(scan, rs, B=3, max_ref=12, n_way=3, starts=None):
+    """RxR-style episodes: as rollout_episodes, but the ground-truth path is deliberately no shortest path.  It runs from the start
+    viewpoint through `n_way` random waypoints: the concatenation of the shortest paths between them, cut at the first revisit of a
+    viewpoint and at `max_ref` viewpoints."""
+    eps = rollout_episodes(scan, rs, B, 2, starts)
+    n = len(scan.vpids)
+    for ep in eps:
+        path = [ep['path'][0]]
+        for w in rs.randint(0, n, n_way):
+            path += scan.shortest_path(path[-1], scan.vpids[int(w)])[1:]
+        cut = next((k for k, vp in enumerate(path) if vp in path[:k]), len(path))
+        ep['path'] = path[:min(cut, max_ref)]
+    return eps
+
+
 def reverie_episodes(scan, objects, rs, B=3, max_steps=5, starts=None):
     """REVERIE-style episodes (M/reverie/env.py:136-151): rollout_episodes plus a target object — one of the objects the path's last
     viewpoint sees (None where it sees none) — and `end_vps`, the viewpoints the target can be seen from (here: the last viewpoint and,
