@@ -332,7 +332,9 @@ int goat_dict_finish(void* stream, int out_dtype, const float* sum, const float*
  * loss[m] = logsumexp(logits[m,:N]) - logits[m,target[m]], lse saved.  Replaces F.cross_entropy on the 576 x 50265
  * MLM scores (P/model/pretrain_goat.py:213-215).  Backward writes dlogits (GOAT_BF16 or GOAT_F32) with row stride
  * ld_out, zeros in the padding columns [N, ld_out), ready to be the K-padded operand of the decoder's dgrad/wgrad.
- * A negative target marks an ignored row (loss 0, zero gradient): the padding rows of a shape-bucketed static batch. */
+ * A negative target marks an ignored row (loss 0, zero gradient): the padding rows of a shape-bucketed static batch.
+ * A target >= N (compared as the int64 it is, in both directions) gives a NaN loss and NaN in dlogits[m, :N]; nothing is read out of
+ * bounds. */
 int goat_ce_fwd(void* stream, const float* logits, int64_t ld, int M, int N, const int64_t* targets,
                 float* loss, float* lse);
 int goat_ce_bwd(void* stream, int dtype_out, const float* logits, int64_t ld, int M, int N,
@@ -523,7 +525,8 @@ int goat_optim_advance(void* stream, int64_t* step, float* sq_norm, float* last_
  * NULL: fw = 0.5).  Masks (bytes, any may be NULL): gvis 1 = visited, gvalid 0 = beyond the map, glens map lengths, lmask 1 = masked
  * (1 = valid when lmask_is_valid).  M [B,G,W] float32 logit-fusion matrix (NULL: none).  Outputs float32:
  *   gl = mask(gs * fw), ll = mask(ls * (1 - fw)), fused = gl + M · zero-filled(ll) (+ ll[0] on column 0 when add_stop),
- *   loss[b] = CE(gl, ga) + CE(ll, la) + CE(fused, ga) when loss != NULL (negative label: 0), lse [B,3] saved for the backward.
+ *   loss[b] = CE(gl, ga) + CE(ll, la) + CE(fused, ga) when loss != NULL (negative label: 0; a label >= G for ga, >= W for la,
+ *   compared as the int64 it is: 0 as well, in the loss and in the gradients), lse [B,3] saved for the backward.
  * Replaces the reference's elementwise / masked_fill / bmm / log_softmax chain: P/model/pretrain_goat.py:375-413 (pre-training),
  * M/models/vilmodel_GOAT.py:803-839 (fine-tuning: add_stop = 1, lmask = vp_nav_masks with lmask_is_valid = 1).
  * Backward: upstream dloss [B] (with the labels) and / or dgl, dll, dfused (NULL = zero) -> dgs, dls (dtype), dfwl (when fwl). */

@@ -1,6 +1,6 @@
 """The small non-GEMM kernels of csrc/causal.hip (attention pooling, door gate, dict_wsum, cfp_mix, InfoNCE, rowdot) and of csrc/embed.hip / csrc/linear_aux.hip
 (panorama fusion, short-K weight gradient, gather / segment mean, embedding tables, column sums) at every dispatch branch, width and tail,
-against float64 references on the CPU.
+against float64 references on the CPU.  (The SAP pair of causal.hip and the cross-entropy kernels: tests/test_loss_heads_gpu.py, with these helpers.)
 
 Reference: float64, from the operands as the kernel receives them (a bf16 input upcast from its bf16 value; the Linear(H, 1) weight of rowdot
 rounded to the activation dtype first), written from the comment block above each kernel; backward references by float64 autograd on the
@@ -76,18 +76,31 @@ def ops():
 
 
 # ================================================================================================ references, conditions, comparison
-def O(ref, kind, odt, zero=None):
-    """one output: float64 reference, 'row' | 'vec' scale, the dtype the kernel stores it in, bool mask of positions compared for equality"""
+def O(ref, kind, odt, zero=None, special=False):
+    """one output: float64 reference, 'row' | 'vec' scale, the dtype the kernel stores it in, bool mask of positions compared for equality.
+    special: positions where the reference is -inf, +inf or NaN are part of the contract (a masked logit, the loss of a label on a masked
+    slot, a poisoned row): the kernel's value must be the same special value, sign included; they take no part in the scales.  Without
+    it a non-finite reference is refused (check_inputs) and a non-finite kernel value is a miss (check), as ever."""
     ref = ref.detach().double()
+    spec = None
+    if special and not bool(torch.isfinite(ref).all()):
+        spec = ref.clone()
+        ref = torch.where(torch.isfinite(ref), ref, torch.zeros_like(ref))
     if zero is None and ref.numel() and not bool(ref.any()):
         zero = torch.ones_like(ref, dtype=torch.bool)         # (the gradients behind a one-slot softmax: exact zeros)
     if zero is not None:
         zero = zero.expand_as(ref).clone()
-    return dict(ref=ref, kind=kind, odt=odt, zero=zero)
+    return dict(ref=ref, kind=kind, odt=odt, zero=zero, spec=spec)
+
+
+def _nonfinite(o):
+    """positions whose reference is a special value (None: none, the default)"""
+    return None if o.get('spec') is None else ~torch.isfinite(o['spec'])
 
 
 def _live(o):
-    return torch.ones_like(o['ref'], dtype=torch.bool) if o['zero'] is None else ~o['zero']
+    live = torch.ones_like(o['ref'], dtype=torch.bool) if o['zero'] is None else ~o['zero']
+    return live if _nonfinite(o) is None else live & ~_nonfinite(o)
 
 
 def row_scale(o):
@@ -95,6 +108,17 @@ def row_scale(o):
     if o['kind'] == 'vec' or a.dim() < 2:
         return a.max() if a.numel() else a.sum()
     return a.amax(-1, keepdim=True)
+
+
+def _same_special(spec, got):
+    """got carries spec's special values at spec's non-finite positions, and only there -> bool"""
+    if got is None:
+        return False
+    nf = ~torch.isfinite(spec)
+    if not torch.equal(nf, ~torch.isfinite(got.double())):
+        return False
+    a, b = spec[nf], got.double()[nf]
+    return bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
 
 
 def check_inputs(dt, outs, what):
@@ -149,6 +173,9 @@ def check_conditioning(dt, outs, outs_f32, what):
     tol, figs = _tol(dt), {}
     for name, o in outs.items():
         scale, live = row_scale(o), _live(o)
+        if _nonfinite(o) is not None or _nonfinite(outs_f32[name]) is not None:
+            assert o.get('spec') is not None and _same_special(o['spec'], outs_f32[name].get('spec')), \
+                '%s %s: float32 on the CPU has other special values than the float64 reference' % (what, name)
         err = ((outs_f32[name]['ref'] - o['ref']).abs() / scale.clamp_min(1e-300)) * live
         figs[name] = float(err.max()) if err.numel() else 0.0
         assert figs[name] <= 0.25 * tol, '%s %s: float32 on the CPU is %.3e of the row scale off the float64 reference: another seed' % (what, name, figs[name])
@@ -165,6 +192,16 @@ def check(group, dt, cid, outs, got, base=None, tag=''):
         g = g.detach().cpu().reshape(ref.shape)
         b = base[name].reshape(ref.shape) if base is not None and name in base else None
         label = '%s %s %s %s%s' % (group, _dn(dt), cid, name, tag)
+        nf = _nonfinite(o)
+        if nf is not None:                                       # special values: the same value with its sign, exactly; then out of the way
+            gs = torch.where(nf, g.double(), torch.full_like(ref, float('inf')))
+            ws = torch.where(nf, o['spec'], torch.full_like(ref, float('inf')))
+            bad = ~((gs == ws) | (torch.isnan(gs) & torch.isnan(ws)))
+            if bool(bad.any()):
+                i = bad.nonzero()[0].tolist()
+                misses.append('%s: %d positions differ from the special value of the reference, first %s: %r for %r' % (
+                    label, int(bad.sum()), i, float(g[tuple(i)]), float(o['spec'][tuple(i)])))
+            g = torch.where(nf, torch.zeros_like(g), g)
         if not bool(torch.isfinite(g).all()):
             print('FIG %s nan' % label)
             misses.append('%s: %d values not finite' % (label, int((~torch.isfinite(g)).sum())))

@@ -423,7 +423,7 @@ __global__ __launch_bounds__(64) void sap_fwd_kernel(SapArgs p) {
     if (lane == 0) {
       p.lse[b * 3] = lg; p.lse[b * 3 + 1] = lw; p.lse[b * 3 + 2] = lf;
       if (p.loss) {
-        const int ga = p.ga ? (int)p.ga[b] : -1, la = p.la ? (int)p.la[b] : -1;
+        const int64_t ga = p.ga ? p.ga[b] : -1, la = p.la ? p.la[b] : -1;       // compared at their full width: a label past the row contributes nothing
         float l = 0.f;
         if (ga >= 0 && ga < p.G) l += (lg - s_gl[ga]) + (lf - s_fu[ga]);
         if (la >= 0 && la < p.W) l += lw - s_ll[la];
@@ -444,7 +444,7 @@ __global__ __launch_bounds__(64) void sap_bwd_kernel(SapArgs p) {
   T* dgs = reinterpret_cast<T*>(p.dgs) + (int64_t)b * p.G;
   T* dls = reinterpret_cast<T*>(p.dls) + (int64_t)b * p.W;
   const float dl = p.dloss ? p.dloss[b] : 0.f;
-  const int ga = (p.dloss && p.ga) ? (int)p.ga[b] : -1, la = (p.dloss && p.la) ? (int)p.la[b] : -1;
+  const int64_t ga = (p.dloss && p.ga) ? p.ga[b] : -1, la = (p.dloss && p.la) ? p.la[b] : -1;
   const bool use_g = ga >= 0 && ga < p.G, use_l = la >= 0 && la < p.W;
   const float lg = p.lse ? p.lse[b * 3] : 0.f, lw = p.lse ? p.lse[b * 3 + 1] : 0.f, lf = p.lse ? p.lse[b * 3 + 2] : 0.f;
   float acc_fw = 0.f;

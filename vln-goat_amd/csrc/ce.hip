@@ -57,8 +57,8 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
   const int m = blockIdx.x;
   const float* row = logits + (int64_t)m * ld;
   T* out = dlogits + (int64_t)m * ld_out;
-  const int t = (int)targets[m];
-  const float l = lse[m], g = t < 0 ? 0.f : (t < N ? dloss[m] : __builtin_nanf(""));      // ignored row: zero gradient; out-of-range target: NaN (see ce_fwd_kernel)
+  const int64_t t = targets[m];                                                            // compared at its full width, as ce_fwd_kernel does
+  const float l = lse[m], g = t < 0 ? 0.f : (t < (int64_t)N ? dloss[m] : __builtin_nanf(""));      // ignored row: zero gradient; out-of-range target: NaN (see ce_fwd_kernel)
   for (int c = threadIdx.x * 4; c < (int)ld_out; c += 256 * 4) {
     float v[4];
 #pragma unroll
