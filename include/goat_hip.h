@@ -717,6 +717,40 @@ int goat_nav_expert_doubles(int cap, int max_ref);
 int goat_nav_ndtw(void* stream, const int64_t* scan_tab, const int64_t* step_tab, int32_t* si, double* sd, int32_t* log,
                   const int32_t* ref, double* xd, int t, int B, int T, int W, int cap, int max_ref, int64_t ignoreid);
 
+/* goat_nav_obj_*: goat_nav_reset / goat_nav_step for a REVERIE / SOON walk (M/reverie/agent_obj_goat.py:180-436), whose panoramas carry
+ * up to O object tokens behind their W views (WT = W + O).  The step differs from goat_nav_step where EpisodePlanner.build_step branches
+ * on its objects: the pool rows of a step are B * WT + B; loc_fts [B, WT, A + 3] and nav_types [B, WT] hold, behind the view_len views,
+ * [angle_feature(direction - the snapped view's angles) | box] and type 2 per object; vp_masks, vp_nav_masks, vp_pos_fts and nav_fusion
+ * are WT + 2 wide; gmap_masks[:, 1] stays true (the REVERIE builder keeps [MEM] selectable; choosing it is still status 3); the label
+ * is the shortest-path expert's.  The same two launches: one workgroup per episode, one for the batch-wide tables.
+ *   obj_tab    device int64 [5]: addresses of the static object tables in the order navdev.ObjectTables packs them, indexed by the
+ *              viewpoint numbers of scan_tab: object CSR start int32 [NV + 1], first row of the viewpoint in ObjectStore.table int32
+ *              [NV] (its rows are contiguous), and per object direction float64 [N, 2], box float32 [N, 3] (h / 480, w / 640, their
+ *              float32 product), category int64 [N].
+ *   step_tab   as goat_nav_step at panorama width WT (feat_idx / feat_start stay [B * W] / [B * W + 1]).
+ *   ostep_tab  device int64 [10]: obj_idx int32 [B * O], obj_start int32 [B * O + 1], reverie_obj_lens int64 [B], reverie_obj_names
+ *              int64 [B, O], vp_obj_masks bool [B, WT + 2], obj_target int64 [B] (slot of the target object on one of the episode's
+ *              goal viewpoints, else ignoreid), ocat_idx int32 [B * WT], ocat_start int32 [B * WT + 1], ocat_inv_idx int32 [B * WT],
+ *              ocat_inv_start int32 [B * W + B * O + 1].  Every element, padding included, is written.  NULL when t == T.
+ *   goal       int32 [B, max_end, 2]: per episode its goal viewpoints (-1: unused pair) and the index of the target object among each
+ *              one's objects (-1: not there).  Read every step; not copied into the state.
+ *   si         B blocks of goat_nav_obj_state_ints(T, W, O, cap) int32; sd and log as goat_nav_step.  Header words 22 / 23 of a log
+ *              block: 1 + the viewpoint of the best stop node at the forced end of an argmax walk (0: no node was scored) and its best
+ *              object (row 2 of act, recorded per scored node; -1 where the viewpoint has no objects: the row is not read there).
+ *   ws         int32 workspace of 2 (B + 1) + T (B WT + B) + B + 1 + (B + 1) words; the live count is word 2 (B + 1) + T (B WT + B) + B.
+ * Status word 5: a viewpoint with more than O objects (clamped).
+ * GOAT_E_ARG: a null pointer (as goat_nav_step; obj_tab, goal; ostep_tab for t < T); GOAT_E_SHAPE: O < 1 or > GOAT_NAV_MAX_O, max_end
+ * outside 1..GOAT_NAV_MAX_END, and everything goat_nav_step rejects.  Both are returned before any launch.  goat_nav_obj_state_ints is a
+ * value (0 outside the limits).  The read-back block keeps the size goat_nav_log_ints(T, cap). */
+#define GOAT_NAV_MAX_O 64
+#define GOAT_NAV_MAX_END 64
+int goat_nav_obj_state_ints(int T, int W, int O, int cap);
+int goat_nav_obj_reset(void* stream, const int64_t* scan_tab, int32_t* si, double* sd, int32_t* log, const int32_t* ep, int B, int T,
+                       int W, int O, int cap);
+int goat_nav_obj_step(void* stream, const int64_t* scan_tab, const int64_t* obj_tab, const int64_t* step_tab, const int64_t* ostep_tab,
+                      int32_t* si, double* sd, int32_t* log, int32_t* ws, const void* act, const double* u, const int32_t* goal, int mode,
+                      int t, int B, int T, int G_prev, int G, int W, int O, int max_end, int A, int cap, int64_t ignoreid);
+
 #ifdef __cplusplus
 }
 #endif

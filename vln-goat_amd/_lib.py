@@ -100,6 +100,10 @@ SIGNATURES = {
     'goat_nav_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i64],
     'goat_nav_expert_doubles': [_i32, _i32],
     'goat_nav_ndtw': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64],
+    'goat_nav_obj_state_ints': [_i32, _i32, _i32, _i32],
+    'goat_nav_obj_reset': [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32],
+    'goat_nav_obj_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                          _i32, _i32, _i64],
 }
 
 

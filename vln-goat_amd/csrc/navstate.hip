@@ -105,6 +105,64 @@ extern "C" int goat_nav_step(void* stream, const int64_t* scan_tab, const int64_
   return 0;
 }
 
+// goat_nav_obj_*: the same two kernels over a REVERIE / SOON walk.  Args::O > 0 turns on the places where EpisodePlanner.build_step
+// branches on its objects: the panorama is W views + O object slots wide, the pool stride of the node embeddings follows it, the
+// object tables of the step are written beside the 21 others, [MEM] stays selectable, and an argmax walk records the best object
+// of every scored node.  One object slot per thread for loc_fts; the tail forms the object CSRs from the same prefix sums.
+namespace {
+
+int nav_obj_sizes_bad(int B, int T, int W, int O, int cap) {
+  return nav_sizes_bad(B, T, W, cap) || O < 1 || O > GOAT_NAV_MAX_O;
+}
+
+}  // namespace
+
+extern "C" int goat_nav_obj_state_ints(int T, int W, int O, int cap) {
+  return nav_obj_sizes_bad(1, T, W, O, cap) ? 0 : Layout(cap, T, W, O).ints;
+}
+
+extern "C" int goat_nav_obj_reset(void* stream, const int64_t* scan_tab, int32_t* si, double* sd, int32_t* log, const int32_t* ep, int B,
+                                  int T, int W, int O, int cap) {
+  if (!scan_tab || !si || !sd || !log || !ep) return GOAT_E_ARG;
+  if (nav_obj_sizes_bad(B, T, W, O, cap)) return GOAT_E_SHAPE;
+  Args a = {};
+  a.scan_tab = scan_tab;
+  a.si = si;
+  a.sd = sd;
+  a.log = log;
+  a.B = B;
+  a.T = T;
+  a.W = W;
+  a.cap = cap;
+  a.O = O;
+  hipLaunchKernelGGL(nav_reset_kernel, dim3(B), dim3(256), 0, ST(stream), a, ep);
+  GOAT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int goat_nav_obj_step(void* stream, const int64_t* scan_tab, const int64_t* obj_tab, const int64_t* step_tab,
+                                 const int64_t* ostep_tab, int32_t* si, double* sd, int32_t* log, int32_t* ws, const void* act,
+                                 const double* u, const int32_t* goal, int mode, int t, int B, int T, int G_prev, int G, int W, int O,
+                                 int max_end, int A, int cap, int64_t ignoreid) {
+  if (!scan_tab || !obj_tab || !si || !sd || !log || !ws || !goal) return GOAT_E_ARG;
+  if (nav_obj_sizes_bad(B, T, W, O, cap) || max_end < 1 || max_end > GOAT_NAV_MAX_END || t < 0 || t > T) return GOAT_E_SHAPE;
+  if (mode != MODE_SAMPLE && mode != MODE_ARGMAX && mode != MODE_FORCED) return GOAT_E_ARG;
+  if (t < T && (!step_tab || !ostep_tab)) return GOAT_E_ARG;
+  if (t > 0 && (!act || (mode == MODE_SAMPLE && !u))) return GOAT_E_ARG;
+  if (t < T && (G < 2 || G > GOAT_NAV_MAX_G || G > cap + 2 || A < 4 || A % 4 != 0 || A > 64)) return GOAT_E_SHAPE;
+  if (t > 0 && (G_prev < 2 || G_prev > GOAT_NAV_MAX_G)) return GOAT_E_SHAPE;
+  Args a = {scan_tab, step_tab, si, sd, log, ws, act, u, mode, t, B, T, G_prev, G, W, A, cap, ignoreid, obj_tab, ostep_tab, goal, O, max_end};
+  // Layout::small + HDR ints: the R2R lists and the best-object record per node, <= 12 KB at the limits (cap = 254, W = 64)
+  const size_t lds = (size_t)(Layout(cap, T, W, O).small + HDR) * sizeof(int32_t);
+  hipLaunchKernelGGL(nav_step_kernel, dim3(B), dim3(256), lds, ST(stream), a);
+  GOAT_LAUNCH_CHECK();
+  if (t < T) {
+    hipLaunchKernelGGL(nav_tail_kernel, dim3(1), dim3(256), 0, ST(stream), a);
+    GOAT_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
 extern "C" int goat_nav_expert_doubles(int cap, int max_ref) {
   return (nav_sizes_bad(1, 1, 1, cap) || max_ref < 1 || max_ref > GOAT_NAV_MAX_REF) ? 0 : expert_doubles(cap, max_ref);
 }

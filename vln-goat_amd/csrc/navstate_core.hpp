@@ -16,8 +16,11 @@ constexpr double NAV_INF = 95959595.0;      // graph_utils.py:45
 constexpr int HDR = 32;
 // header words of an episode (the first HDR ints of its read-back block)
 enum { H_CUR = 0, H_VIEW, H_ENDED, H_JUST, H_N, H_STATUS, H_STATUS_T, H_START, H_GOAL, H_NOLEFT, H_NSCORED, H_LIVE, H_NSLOT, H_VLEN,
-       H_NCAND, H_STARTVIEW, H_HOPN, H_BT_START, H_BT_N, H_K, H_SCAN, H_FOLD /* navexpert_core.hpp: 1 + the hops folded into its DTW row */ };
-enum { ST_OK = 0, ST_MAP = 1, ST_PANO = 2, ST_ACTION = 3, ST_PATH = 4 };
+       H_NCAND, H_STARTVIEW, H_HOPN, H_BT_START, H_BT_N, H_K, H_SCAN, H_FOLD /* navexpert_core.hpp: 1 + the hops folded into its DTW row */,
+       // object walks (Args::O > 0): 1 + the viewpoint of the best stop node at the forced end of an argmax walk (0: never scored), its
+       // best-object record (-1: the viewpoint has no objects), and the objects of the current viewpoint clamped to the bucket O
+       H_PRED_VP, H_PRED_OBJ, H_OLEN };
+enum { ST_OK = 0, ST_MAP = 1, ST_PANO = 2, ST_ACTION = 3, ST_PATH = 4, ST_OBJ = 5 };
 enum { MODE_SAMPLE = 0, MODE_ARGMAX = 1, MODE_FORCED = 2 };
 enum { KIND_NONE = 0, KIND_SET = 1, KIND_ACC = 2 };
 // the static scan tables, in the order of the address table `scan_tab`
@@ -27,18 +30,25 @@ enum { SC_POS = 0, SC_CAND_START, SC_CAND_NB, SC_CAND_POINT, SC_CAND_ANG, SC_CAN
 enum { TB_FEAT_IDX = 0, TB_FEAT_START, TB_LOC_FTS, TB_NAV_TYPES, TB_VIEW_LENS, TB_STEP_IDS, TB_GMAP_POS, TB_PAIR, TB_VISITED, TB_GMASK,
        TB_VP_POS, TB_VP_MASK, TB_VP_NAV, TB_FUSION, TB_TARGET, TB_CSR_IDX, TB_CSR_START, TB_CSR_SCALE, TB_INV_IDX, TB_INV_START, TB_INV_W,
        TB_COUNT };
+// the static object tables (navdev.ObjectTables), in the order of the address table `obj_tab`
+enum { OB_START = 0, OB_ROW, OB_DIR, OB_BOX, OB_NAME, OB_COUNT };
+// the object tables of one step, in the order of the address table `ostep_tab`
+enum { OT_OBJ_IDX = 0, OT_OBJ_START, OT_OBJ_LENS, OT_OBJ_NAMES, OT_VP_OBJ, OT_OBJ_TARGET, OT_OCAT_IDX, OT_OCAT_START, OT_OCAT_INV_IDX,
+       OT_OCAT_INV_START, OT_COUNT };
 
 struct Layout {      // ints of an episode's private state / of its read-back block; navdev.py computes the same numbers
   int cap, T, W, acc;
-  int o_vp, o_vis, o_step, o_kind, o_nacc, o_ord, o_slot, o_scored, o_iscand, o_acc, o_P, o_rows, o_cnode, o_seg, o_stk, small, ints;
+  int o_vp, o_vis, o_step, o_kind, o_nacc, o_ord, o_slot, o_scored, o_iscand, o_acc, o_P, o_rows, o_cnode, o_seg, o_best, o_stk, small, ints;
   int l_hs, l_hops, log_ints;
-  NAV_HD Layout(int cap_, int T_, int W_) : cap(cap_), T(T_), W(W_), acc(T_ + 1) {
+  // O_: the object bucket of a REVERIE / SOON walk (0: no objects, the layout of an R2R walk word for word)
+  NAV_HD Layout(int cap_, int T_, int W_, int O_ = 0) : cap(cap_), T(T_), W(W_), acc(T_ + 1) {
     int o = 0;
     o_vp = o; o += cap;  o_vis = o; o += cap;  o_step = o; o += cap;  o_kind = o; o += cap;  o_nacc = o; o += cap;
     o_ord = o; o += cap;  o_slot = o; o += cap;  o_scored = o; o += cap;  o_iscand = o; o += cap;
     o_rows = o; o += W;  o_cnode = o; o += W;
     o_seg = o; o += cap + 3;
-    small = o;           // everything above is what the serial parts of a step walk over: a kernel may stage it in LDS
+    o_best = o; o += O_ > 0 ? cap : 0;      // argmax walks with objects: the best object of every scored node (-1: it has none)
+    small = o;          // everything above is what the serial parts of a step walk over: a kernel may stage it in LDS
     o_acc = o; o += cap * acc;
     o_P = o; o += cap * cap;
     o_stk = o; o += 2 * cap + 2;
@@ -58,10 +68,17 @@ struct Args {
   const double* u;
   int mode, t, B, T, Gp, G, W, A, cap;
   int64_t ignoreid;
+  // object walks (goat_nav_obj_*); all zero: no objects
+  const int64_t* obj_tab;
+  const int64_t* ostep_tab;     // null when t == T
+  const int32_t* goal;          // [B, max_end, 2]: goal viewpoint (-1: padding), index of the target among its objects or -1
+  int O, max_end;
 };
 
 template <class T> NAV_HD inline const T* scan_ptr(const Args& a, int k) { return reinterpret_cast<const T*>(a.scan_tab[k]); }
 template <class T> NAV_HD inline T* step_ptr(const Args& a, int k) { return reinterpret_cast<T*>(a.step_tab[k]); }
+template <class T> NAV_HD inline const T* obj_ptr(const Args& a, int k) { return reinterpret_cast<const T*>(a.obj_tab[k]); }
+template <class T> NAV_HD inline T* ostep_ptr(const Args& a, int k) { return reinterpret_cast<T*>(a.ostep_tab[k]); }
 
 struct Ep {       // the views of one episode's state
   Layout L;
@@ -73,7 +90,7 @@ struct Ep {       // the views of one episode's state
   double* D;
   double* score;
   int cap;
-  NAV_HD Ep(const Args& a, int b, int32_t* staged = nullptr) : L(a.cap, a.T, a.W), cap(a.cap) {
+  NAV_HD Ep(const Args& a, int b, int32_t* staged = nullptr) : L(a.cap, a.T, a.W, a.O), cap(a.cap) {
     Sb = a.si + (int64_t)b * L.ints;
     int32_t* G = a.log + (int64_t)2 * a.T * a.B + (int64_t)b * L.log_ints;
     S = staged ? staged : Sb;
@@ -245,6 +262,9 @@ NAV_HD inline void advance_episode(const Args& a, const Ep& e, int b, int tp, in
           for (int i = 0; i < e.H[H_NSCORED]; ++i) seen = seen || e.S[e.L.o_scored + i] == ci;
           if (!seen) e.S[e.L.o_scored + e.H[H_NSCORED]++] = ci;
           e.score[ci] = (double)back[a.B + b];
+          // ['og'] = obj_ids[best object] | None: row 2 is read only where the viewpoint has objects (elsewhere it holds the argmax
+          // of an all -inf row less v + 2, a negative number)
+          if (a.O > 0) e.S[e.L.o_best + ci] = e.H[H_OLEN] > 0 ? (int)back[2 * a.B + b] : -1;
         }
       }
     } else {
@@ -297,6 +317,10 @@ NAV_HD inline void advance_episode(const Args& a, const Ep& e, int b, int tp, in
         const int c = e.S[e.L.o_scored + i];
         if (e.score[c] > e.score[best]) best = c;
       }
+      if (a.O > 0) {                        // traj['pred_objid'] = score.get('og')
+        e.H[H_PRED_VP] = e.S[e.L.o_vp + best] + 1;
+        e.H[H_PRED_OBJ] = e.S[e.L.o_best + best];
+      }
       const int ci = e.find(cur);
       if (ci >= 0 && best != ci) {
         const int room = (a.T + 1) * cap - hopn;
@@ -342,6 +366,7 @@ template <class Sync>
 NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int nt, Sync sync) {
 #pragma clang fp contract(off)
   const int cap = a.cap, t = a.t, B = a.B, G = a.G, W = a.W, A = a.A, C = a.A + 3;
+  const int O = a.O, WT = W + O;        // object walks: O object slots behind the W views of every panorama (panorama_object_inputs)
   const Layout& L = e.L;
   int32_t* S = e.S;
   const int32_t* cs = scan_ptr<int32_t>(a, SC_CAND_START);
@@ -349,7 +374,7 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
   const int32_t* pt = scan_ptr<int32_t>(a, SC_CAND_POINT);
   const int ended = e.H[H_ENDED], cur = e.H[H_CUR], view = e.H[H_VIEW];
   const int c0 = cs[cur];
-  const int view_base = t * (B * W + B), fused_base = view_base + B * W;
+  const int view_base = t * (B * WT + B), fused_base = view_base + B * WT;      // store.advance(B, te.WT)
   if (tid == 0) {
     if (!ended) e.H[H_LIVE] += 1;
     // panorama_inputs: the candidates' views, then the views no candidate used
@@ -373,6 +398,15 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
     }
     e.H[H_VLEN] = len;
     e.H[H_NCAND] = ncand < W ? ncand : W;
+    if (O > 0) {      // the objects of the viewpoint: contiguous rows of ObjectStore.table
+      const int32_t* os = obj_ptr<int32_t>(a, OB_START);
+      int olen = os[cur + 1] - os[cur];
+      if (olen > O) {
+        e.fail(ST_OBJ, t);
+        olen = O;
+      }
+      e.H[H_OLEN] = olen;
+    }
     // note_step (nav_inputs.py:233-243)
     const int n = e.H[H_N];
     for (int i = 0; i < n; ++i) S[L.o_iscand + i] = 0;
@@ -389,7 +423,7 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
       if (j < 0) continue;
       S[L.o_iscand + j] = 1;
       if (!ended && !S[L.o_vis + j]) {            // NodeEmbedStore.accumulate
-        const int row = view_base + b * W + c;
+        const int row = view_base + b * WT + c;
         int32_t* acc = e.Sb + L.o_acc + j * L.acc;
         if (S[L.o_kind + j] == KIND_NONE) {
           S[L.o_kind + j] = KIND_ACC;
@@ -443,6 +477,23 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
     }
     step_ptr<int64_t>(a, TB_TARGET)[b] = target;
     step_ptr<int64_t>(a, TB_VIEW_LENS)[b] = len;
+    if (O > 0) {
+      // teacher_object (nav_inputs.py:175-186): on one of the episode's end viewpoints the slot of the target object among [stop],
+      // [MEM], the views and the objects; the ignore value elsewhere and where the target is not among the viewpoint's objects
+      const int olen = e.H[H_OLEN];
+      int64_t ot = a.ignoreid;
+      if (!ended) {
+        const int32_t* goal = a.goal + (int64_t)b * a.max_end * 2;
+        for (int k = 0; k < a.max_end; ++k)
+          if (goal[2 * k] == cur) {         // (a viewpoint listed twice carries the same index)
+            const int j = goal[2 * k + 1];
+            if (j >= 0 && j < olen) ot = j + len + 2;
+            break;
+          }
+      }
+      ostep_ptr<int64_t>(a, OT_OBJ_TARGET)[b] = ot;
+      ostep_ptr<int64_t>(a, OT_OBJ_LENS)[b] = olen;
+    }
     // the episode's share of the node-embedding CSR (NodeEmbedStore.csr): tokens per slot as a running sum
     int tok = 0;
     S[L.o_seg] = 0;
@@ -463,12 +514,23 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
     const double* cang = scan_ptr<double>(a, SC_CAND_ANG);
     const float* vaf = scan_ptr<float>(a, SC_VAF);
     const int fr36 = scan_ptr<int32_t>(a, SC_FEATURE_ROW)[cur] * 36;
-    float* loc = step_ptr<float>(a, TB_LOC_FTS) + (int64_t)b * W * C;
-    int64_t* ty = step_ptr<int64_t>(a, TB_NAV_TYPES) + (int64_t)b * W;
-    uint8_t* vm = step_ptr<uint8_t>(a, TB_VP_MASK) + (int64_t)b * (W + 2);
-    uint8_t* vn = step_ptr<uint8_t>(a, TB_VP_NAV) + (int64_t)b * (W + 2);
-    for (int j = tid; j < W; j += nt) {
+    float* loc = step_ptr<float>(a, TB_LOC_FTS) + (int64_t)b * WT * C;
+    int64_t* ty = step_ptr<int64_t>(a, TB_NAV_TYPES) + (int64_t)b * WT;
+    uint8_t* vm = step_ptr<uint8_t>(a, TB_VP_MASK) + (int64_t)b * (WT + 2);
+    uint8_t* vn = step_ptr<uint8_t>(a, TB_VP_NAV) + (int64_t)b * (WT + 2);
+    const int olen = O > 0 ? e.H[H_OLEN] : 0;
+    const int o0 = O > 0 ? obj_ptr<int32_t>(a, OB_START)[cur] : 0;
+    for (int j = tid; j < WT; j += nt) {
       float* row = loc + j * C;
+      if (j >= vlen && j < vlen + olen) {
+        // ObjectStore.attributes: the object tokens follow the views (nav type 2): [angle_feature(direction - base) | box]
+        const double* dir = obj_ptr<double>(a, OB_DIR) + (int64_t)(o0 + j - vlen) * 2;
+        const float* box = obj_ptr<float>(a, OB_BOX) + (int64_t)(o0 + j - vlen) * 3;
+        angle_row(row, A, dir[0] - bh, dir[1] - be);
+        for (int x = 0; x < 3; ++x) row[A + x] = box[x];
+        ty[j] = 2;
+        continue;
+      }
       if (j < ncand) {
         angle_row(row, A, cang[(c0 + j) * 2] - bh, cang[(c0 + j) * 2 + 1] - be);
       } else if (j < vlen) {
@@ -480,9 +542,17 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
       for (int x = A; x < C; ++x) row[x] = j < vlen ? 1.0f : 0.0f;
       ty[j] = j < ncand ? 1 : 0;
     }
-    for (int j = tid; j < W + 2; j += nt) {
-      vm[j] = j < vlen + 2;
+    for (int j = tid; j < WT + 2; j += nt) {
+      vm[j] = j < vlen + olen + 2;
       vn[j] = j == 0 ? 1 : (j == 1 ? 0 : (j - 2 < ncand));
+    }
+    if (O > 0) {
+      uint8_t* vo = ostep_ptr<uint8_t>(a, OT_VP_OBJ) + (int64_t)b * (WT + 2);
+      int64_t* names = ostep_ptr<int64_t>(a, OT_OBJ_NAMES) + (int64_t)b * O;
+      const int64_t* name = obj_ptr<int64_t>(a, OB_NAME);
+      // vp_inputs: the head of vp_nav_masks ([stop] true, [MEM] false), then nav_types == 2
+      for (int j = tid; j < WT + 2; j += nt) vo[j] = j == 0 ? 1 : (j - 2 >= vlen && j - 2 < vlen + olen);
+      for (int j = tid; j < O; j += nt) names[j] = j < olen ? name[o0 + j] : 0;
     }
   }
   // ---- map tokens (gmap_inputs, GraphMap.get_pos_fts / pair_dists)
@@ -502,7 +572,7 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
       const int node = real ? S[L.o_ord + g - 2] : -1;
       sid[g] = real ? S[L.o_step + node] : 0;
       vmask[g] = g == 1 ? 1 : (real ? S[L.o_vis + node] != 0 : 0);
-      gmask[g] = g < nslots && g != 1;
+      gmask[g] = g < nslots && (g != 1 || O > 0);      // (gmap_inputs(mem_selectable=has_obj): the REVERIE builder keeps [MEM])
       scale[g] = (real && S[L.o_kind + node] == KIND_ACC) ? (float)(1.0 / (double)S[L.o_nacc + node]) : 1.0f;
       if (g >= nslots) {
         for (int x = 0; x < C; ++x) row[x] = 0.0f;
@@ -544,9 +614,9 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
       pair[x] = v;
     }
     // nav_fusion_matrix (nav_model.py:231-253)
-    float* fus = step_ptr<float>(a, TB_FUSION) + (int64_t)b * G * (W + 2);
-    for (int x = tid; x < G * (W + 2); x += nt) {
-      const int g = x / (W + 2), j = x % (W + 2);
+    float* fus = step_ptr<float>(a, TB_FUSION) + (int64_t)b * G * (WT + 2);
+    for (int x = tid; x < G * (WT + 2); x += nt) {
+      const int g = x / (WT + 2), j = x % (WT + 2);
       float v = 0.0f;
       if (g >= 2 && g < nslots && j >= 2 && j - 2 < ncand) {
         const int node = S[L.o_ord + g - 2], cn = S[L.o_cnode + j - 2];
@@ -562,10 +632,10 @@ NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int
   // ---- vp_inputs: the start node's row in every slot, the candidates' rows behind it (rows of gmap_pos_fts)
   {
     const float* gp = step_ptr<float>(a, TB_GMAP_POS) + (int64_t)b * G * C;
-    float* vp = step_ptr<float>(a, TB_VP_POS) + (int64_t)b * (W + 2) * 2 * C;
+    float* vp = step_ptr<float>(a, TB_VP_POS) + (int64_t)b * (WT + 2) * 2 * C;
     const int sn = e.find(e.H[H_START]);
     const int sslot = sn >= 0 ? S[L.o_slot + sn] : G;
-    for (int x = tid; x < (W + 2) * 2 * C; x += nt) {
+    for (int x = tid; x < (WT + 2) * 2 * C; x += nt) {
       const int j = x / (2 * C), c = x % (2 * C);
       float v = 0.0f;
       if (c < C) {
@@ -604,11 +674,14 @@ NAV_HD inline void step_episode(const Args& a, int b, int tid, int nt, Sync sync
 }
 
 // The batch-wide tail of a step: the compact CSRs are prefix sums over the episodes (episodes.py:_compact_rows, NodeEmbedStore.csr,
-// graphmap.inverse_index).  One group of threads; `part` holds nt ints they share.  ws: [2 * (B + 1)] bases, one owner per pool row, the live count.
+// graphmap.inverse_index).  One group of threads; `part` holds nt ints they share.  ws: [2 * (B + 1)] bases, one owner per pool row, the live count and,
+// with objects, [B + 1] object bases behind it.
 template <class Sync>
 NAV_HD inline void nav_tail(const Args& a, int32_t* part, int tid, int nt, Sync sync) {
-  const int B = a.B, G = a.G, W = a.W, t = a.t;
-  const int rows = (t + 1) * (B * W + B), n_src = rows + (t > 0 ? B : 0);
+  const int B = a.B, G = a.G, W = a.W, t = a.t, O = a.O, WT = a.W + a.O;
+  const int rows = (t + 1) * (B * WT + B), n_src = rows + (t > 0 ? B : 0);
+  const int live_at = 2 * (B + 1) + a.T * (B * WT + B) + B;
+  int32_t* obase = a.ws + live_at + 1;      // object walks: [B + 1] behind the live count
   int32_t* fbase = a.ws;
   int32_t* cbase = a.ws + B + 1;
   int32_t* owner = a.ws + 2 * (B + 1);
@@ -621,18 +694,23 @@ NAV_HD inline void nav_tail(const Args& a, int32_t* part, int tid, int nt, Sync 
   int32_t* inv_start = step_ptr<int32_t>(a, TB_INV_START);
   float* inv_w = step_ptr<float>(a, TB_INV_W);
   if (tid == 0) {
-    int f = 0, c = 0, live = 0;
+    int f = 0, c = 0, live = 0, o = 0;
     for (int b = 0; b < B; ++b) {
       Ep e(a, b);
       fbase[b] = f;
       cbase[b] = c;
+      if (O > 0) {
+        obase[b] = o;
+        o += e.H[H_OLEN];
+      }
       f += e.H[H_VLEN];
       c += e.S[e.L.o_seg + G];
       live += !e.H[H_ENDED];
     }
     fbase[B] = f;
     cbase[B] = c;
-    a.ws[2 * (B + 1) + a.T * (B * W + B) + B] = live;      // episodes still walking when step t begins (an optional host read)
+    if (O > 0) obase[B] = o;
+    a.ws[live_at] = live;      // episodes still walking when step t begins (an optional host read)
   }
   for (int r = tid; r < n_src; r += nt) owner[r] = -1;
   sync();
@@ -649,6 +727,54 @@ NAV_HD inline void nav_tail(const Args& a, int32_t* part, int tid, int nt, Sync 
     feat_start[B * W] = ftot;
     csr_start[B * G] = ctot;
     inv_start[n_src] = ctot;
+  }
+  if (O > 0) {
+    // _compact_rows(obj_rows) and _obj_concat_tables (graphmap.build_obj_concat_index / inverse_index): token J of panorama b is view J
+    // (source row b * W + J) or object J - view_len (source row B * W + b * O + J - view_len).  A source row is read by at most one
+    // token and the tokens of a panorama read ascending rows, so the inverse lists the views of all panoramas, then their objects.
+    const int32_t* orow = obj_ptr<int32_t>(a, OB_ROW);
+    int32_t* obj_idx = ostep_ptr<int32_t>(a, OT_OBJ_IDX);
+    int32_t* obj_start = ostep_ptr<int32_t>(a, OT_OBJ_START);
+    int32_t* cat_idx = ostep_ptr<int32_t>(a, OT_OCAT_IDX);
+    int32_t* cat_start = ostep_ptr<int32_t>(a, OT_OCAT_START);
+    int32_t* cinv_idx = ostep_ptr<int32_t>(a, OT_OCAT_INV_IDX);
+    int32_t* cinv_start = ostep_ptr<int32_t>(a, OT_OCAT_INV_START);
+    const int otot = obase[B], ttot = ftot + otot;
+    for (int s = tid; s < B * O; s += nt) {
+      const int b = s / O, j = s % O;
+      Ep e(a, b);
+      const int ol = e.H[H_OLEN], at = obase[b] + (j < ol ? j : ol);
+      obj_start[s] = at;
+      cinv_start[B * W + s] = ftot + at;
+      if (j < ol) {
+        obj_idx[at] = orow[e.H[H_CUR]] + j;
+        cinv_idx[ftot + at] = b * WT + e.H[H_VLEN] + j;
+      }
+      if (s >= otot) obj_idx[s] = -1;
+    }
+    for (int s = tid; s < B * W; s += nt) {
+      const int b = s / W, j = s % W;
+      Ep e(a, b);
+      const int vl = e.H[H_VLEN], at = fbase[b] + (j < vl ? j : vl);
+      cinv_start[s] = at;
+      if (j < vl) cinv_idx[at] = b * WT + j;
+    }
+    for (int s = tid; s < B * WT; s += nt) {
+      const int b = s / WT, j = s % WT;
+      Ep e(a, b);
+      const int vl = e.H[H_VLEN], n = vl + e.H[H_OLEN], at = fbase[b] + obase[b] + (j < n ? j : n);
+      cat_start[s] = at;
+      if (j < n) cat_idx[at] = j < vl ? b * W + j : B * W + b * O + (j - vl);
+      if (s >= ttot) {
+        cat_idx[s] = -1;
+        cinv_idx[s] = -1;
+      }
+    }
+    if (tid == 0) {
+      obj_start[B * O] = otot;
+      cat_start[B * WT] = ttot;
+      cinv_start[B * W + B * O] = ttot;
+    }
   }
   for (int s = tid; s < B * G; s += nt) {
     const int b = s / G, g = s % G;

@@ -168,10 +168,11 @@ class NavEvaluator:
         return avg, metrics
 
 
-def validate(walk, evaluator, episode_batches):
+def validate(walk, evaluator, episode_batches, navigator=None, check_every=None):
     """The validation pass of the reference trainer (M/r2r/main_nav.py `valid`: agent.test() with argmax feedback, then
     env.eval_metrics) over captured graphs: `walk` (rollout.ArgmaxEpisode) is replayed for every batch of `episode_batches`; a batch
     shorter than the walk's B (the last one) is padded with repeats of its first episode, whose predictions are dropped.
+    navigator / check_every: passed to `walk.run` (a navdev.DeviceNavigator in 'argmax' mode paces the walk on the device).
     -> (avg_metrics, metrics, preds)."""
     B = walk.B
     preds = []
@@ -180,7 +181,8 @@ def validate(walk, evaluator, episode_batches):
         n = len(episodes)
         if not 1 <= n <= B:
             raise ValueError('validate: a batch of %d episodes for a walk captured at B = %d' % (n, B))
-        traj = walk.run(episodes + [episodes[0]] * (B - n))
+        padded = episodes + [episodes[0]] * (B - n)
+        traj = walk.run(padded) if (navigator is None and check_every is None) else walk.run(padded, navigator=navigator, check_every=check_every)
         for tr in traj[:n]:
             item = {'instr_id': tr['instr_id'], 'trajectory': tr['path']}
             if 'pred_objid' in tr:

@@ -18,8 +18,16 @@ The DAgger labels follow `te.expert_policy`: 'spl' comes out of `goat_nav_step` 
 step, `goat_nav_ndtw` (csrc/navexpert_core.hpp), writes the nDTW expert's label over it from the walked path it folds forward on the
 device and the episode's ground-truth path, staged by begin() in a bucket of `max_ref` viewpoints.
 
-Scope: R2R- and RxR-style walks.  The REVERIE / SOON object tables (`te.objects`) stay on the host planner, and so does the two-pass
-`SampledEpisode`, which needs finish()'s joined `all_*` tables and is the slower form of the sampled half anyway."""
+A TeacherEpisode with REVERIE / SOON objects (`te.objects`) walks through `goat_nav_obj_step`, the same two launches with the object
+bucket O = te.O switched on: `ObjectTables` holds the static object half (directions, boxes, categories, rows of ObjectStore.table),
+`DeviceNavigator(..., objects=ObjectTables(te.objects, tables), max_end=)` writes the ten object tables of a step beside the 21 others,
+begin() stages the goals (`object_goals`: end viewpoints and the target's index among their objects), and an argmax walk returns
+`pred_objid` as the host planner does.
+
+Scope: R2R-, RxR- and REVERIE-style walks.  Object walks hold at most 64 objects per viewpoint and 64 end viewpoints per episode, and
+their episodes carry an explicit `obj_id` (or the simulator runs with obj_fallback=False): the stand-in target the host draws per
+observation from `sim.obj_rng` cannot be restated by a kernel.  The two-pass `SampledEpisode` stays on the host planner: it needs
+finish()'s joined `all_*` tables and is the slower form of the sampled half anyway."""
 import time
 
 import numpy as np
@@ -42,8 +50,31 @@ STEP_TABLES = (('feat_idx', torch.int32), ('feat_start', torch.int32), ('loc_fts
                ('vp_nav_masks', torch.bool), ('nav_fusion', torch.float32), ('target', torch.int64), ('csr_idx', torch.int32),
                ('csr_start', torch.int32), ('csr_scale', torch.float32), ('inv_idx', torch.int32), ('inv_start', torch.int32),
                ('inv_w', torch.float32))
-H_ENDED, H_STATUS, H_STATUS_T, H_LIVE, H_HOPN, H_BT_START, H_BT_N, HDR = 2, 5, 6, 11, 16, 17, 18, 32
+H_ENDED, H_STATUS, H_STATUS_T, H_LIVE, H_HOPN, H_BT_START, H_BT_N, H_PRED_VP, H_PRED_OBJ, HDR = 2, 5, 6, 11, 16, 17, 18, 22, 23, 32
 MAX_B, MAX_T, MAX_G, MAX_W, MAX_CAP, MAX_REF = 1024, 64, 256, 64, 254, 64        # GOAT_NAV_MAX_* (include/goat_hip.h)
+MAX_O, MAX_END = 64, 64
+STATUS[5] = 'the viewpoint has more objects than the bucket obj_width'
+OBJECT_TABLES = ('obj_start', 'obj_row', 'obj_dir', 'obj_box', 'obj_name')
+OBJECT_STEP_TABLES = (('obj_idx', torch.int32), ('obj_start', torch.int32), ('reverie_obj_lens', torch.int64), ('reverie_obj_names', torch.int64),
+                      ('vp_obj_masks', torch.bool), ('obj_target', torch.int64), ('ocat_idx', torch.int32), ('ocat_start', torch.int32),
+                      ('ocat_inv_idx', torch.int32), ('ocat_inv_start', torch.int32))
+
+
+def _pack(host, names, device):
+    """one packed buffer, one H2D copy -> (the buffer, the addresses of the tables inside it as a device int64 tensor)"""
+    offs, n = [], 0
+    for name in names:
+        offs.append(n)
+        n += (max(host[name].nbytes, 1) + 15) // 16 * 16
+    flat = torch.zeros(n, dtype=torch.uint8)
+    for name, o in zip(names, offs):
+        raw = np.ascontiguousarray(host[name]).view(np.uint8).reshape(-1)
+        flat[o:o + raw.size] = torch.from_numpy(raw)
+    if device.type == 'cuda':
+        flat = flat.pin_memory()
+    dev = flat.to(device, non_blocking=True)
+    base = dev.data_ptr()
+    return dev, torch.tensor([base + o for o in offs], dtype=torch.int64).to(device)
 
 
 class ScanTables:
@@ -100,19 +131,68 @@ class ScanTables:
 
     def _upload(self):
         """one packed buffer, one H2D copy; `tab` = the addresses of the tables inside it (device int64 [15])"""
-        offs, n = [], 0
-        for name in SCAN_TABLES:
-            offs.append(n)
-            n += (max(self.host[name].nbytes, 1) + 15) // 16 * 16
-        flat = torch.zeros(n, dtype=torch.uint8)
-        for name, o in zip(SCAN_TABLES, offs):
-            raw = np.ascontiguousarray(self.host[name]).view(np.uint8).reshape(-1)
-            flat[o:o + raw.size] = torch.from_numpy(raw)
-        if self.device.type == 'cuda':
-            flat = flat.pin_memory()
-        self.dev = flat.to(self.device, non_blocking=True)
-        base = self.dev.data_ptr()
-        self.tab = torch.tensor([base + o for o in offs], dtype=torch.int64).to(self.device)
+        self.dev, self.tab = _pack(self.host, SCAN_TABLES, self.device)
+
+
+class ObjectTables:
+    """The static object half of REVERIE / SOON observations for `goat_nav_obj_step`, as ScanTables holds the view half: indexed by the
+    viewpoint numbers of `tables` (a ScanTables).  objects: an ObjectStore or its `.meta()` (no feature table is read).  Per viewpoint
+    `obj_start` int32 [V + 1] (CSR over the objects below) and `obj_row` int32 [V], the viewpoint's first row in ObjectStore.table (its
+    rows are contiguous: `attributes` returns an arange); per object `obj_dir` float64 [N, 2] (the stored directions), `obj_box` float32
+    [N, 3] formed as `ObjectStore.attributes` forms them (h / 480 and w / 640 rounded to float32, their float32 product: independent of the
+    heading) and `obj_name` int64 [N].  `ids[v]`: the object ids of viewpoint v on the host (for `pred_objid`).  device=None keeps the
+    tables on the host only (`.host`)."""
+
+    def __init__(self, objects, tables, device='cuda'):
+        self.tables = tables
+        start, row, dirs, box, name, self.ids = [0], [], [], [], [], []
+        for sc in tables.scans:
+            for vp in sc.vpids:
+                k = '%s_%s' % (sc.name, vp)
+                o, a = objects.count.get(k, 0), objects.attrs.get(k)
+                row.append(objects.start.get(k, 0))
+                self.ids.append(list(a['obj_ids'])[:o] if o else [])
+                if o:
+                    b = np.zeros((o, 3), np.float32)
+                    b[:, 0], b[:, 1] = a['sizes'][:o, 1] / 480, a['sizes'][:o, 0] / 640
+                    b[:, 2] = b[:, 0] * b[:, 1]
+                    dirs.append(np.asarray(a['directions'][:o], np.float64))
+                    box.append(b)
+                    name.append(np.asarray(a['names'][:o], np.int64))
+                start.append(start[-1] + o)
+        self.host = {'obj_start': np.asarray(start, np.int32), 'obj_row': np.asarray(row, np.int32),
+                     'obj_dir': np.concatenate(dirs, 0) if dirs else np.zeros((0, 2), np.float64),
+                     'obj_box': np.concatenate(box, 0) if box else np.zeros((0, 3), np.float32),
+                     'obj_name': np.concatenate(name) if name else np.zeros(0, np.int64)}
+        self.device = None if device is None else torch.device(device)
+        self.dev, self.tab = None, None
+        if self.device is not None:
+            self.dev, self.tab = _pack(self.host, OBJECT_TABLES, self.device)
+
+
+def object_goals(episodes, objtables, max_end, obj_fallback=False):
+    """The goals of object walks as `goat_nav_obj_step` reads them -> int32 [B, max_end, 2]: per episode its `end_vps` as viewpoint
+    numbers (-1: unused pair) and, per end viewpoint, the index of the target among that viewpoint's objects by the reference's
+    `str(oid) == str(gt_obj_id)` rule (nav_inputs.teacher_object: the first match), or -1 (absent, or `obj_id` None).
+    obj_fallback (te.sim.obj_fallback): the host then draws a stand-in target from `sim.obj_rng` per observation for an episode without
+    `obj_id`, a sequence no kernel can restate: such an episode raises ValueError here."""
+    goals = np.full((len(episodes), max_end, 2), -1, np.int32)
+    tables = objtables.tables
+    for i, e in enumerate(episodes):
+        ends = list(e.get('end_vps') or [])
+        if len(ends) > max_end:
+            raise ValueError('DeviceNavigator: episode %d has %d end viewpoints, the bucket max_end holds %d' % (i, len(ends), max_end))
+        if e.get('obj_id') is None and obj_fallback:
+            raise ValueError('DeviceNavigator: episode %d has no obj_id and the simulator draws a random stand-in target per observation '
+                             '(GraphSim(obj_fallback=True)); the device navigator needs explicit targets or obj_fallback=False' % i)
+        for k, vp in enumerate(ends):
+            v = tables.vp(e['scan'].name, vp)
+            goals[i, k, 0] = v
+            for j, oid in enumerate(objtables.ids[v]):
+                if str(oid) == str(e.get('obj_id')):
+                    goals[i, k, 1] = j
+                    break
+    return goals
 
 
 class DeviceNavigator:
@@ -124,15 +204,21 @@ class DeviceNavigator:
     By hand: begin(episodes, rng | actions) -> for t in 0..T-1: step(t, act) then the step graph -> step(T, act) -> finish().
     max_ref (te.expert_policy = 'ndtw' only): the bucket of the ground-truth path in viewpoints, at most 64; begin() raises ValueError
     for a longer path, before any launch.
+    objects (required when te.objects is set): the ObjectTables of te.objects over the same `tables`; max_end: the bucket of an episode's
+    `end_vps`, at most 64 (begin() raises ValueError for a longer list).  finish() of an argmax walk then adds 'pred_objid' to every
+    trajectory (the id, or None for a viewpoint without objects or a walk that scored no node).
     begin() is one pinned H2D copy (scan, start viewpoint and view, goal per episode; the uniforms `rng.random_sample((T, B))`, the
     numbers the host walk draws step by step, in its order; the forced actions; the ground-truth paths for the nDTW expert) next to the instruction's `txt_ids` / `txt_masks`;
     step() launches the kernels and recomputes, into the same storage and in stream order, the memoised masks derived from the step's
     tables (a raw kernel write does not bump a tensor's version counter); finish() is the one read-back: status words, actions, hop log
     and n_traj.  A non-zero status word is raised there as a ValueError naming episode and step.  Nothing in between synchronises."""
 
-    def __init__(self, te, tables, bufs, mode, max_ref=32):
-        if te.objects is not None:
-            raise NotImplementedError('DeviceNavigator: REVERIE / SOON object tables stay on the host planner (EpisodePlanner)')
+    def __init__(self, te, tables, bufs, mode, max_ref=32, objects=None, max_end=32):
+        if te.objects is not None and objects is None:
+            raise NotImplementedError('DeviceNavigator: a walk with REVERIE / SOON objects needs their device tables: pass '
+                                      'objects=ObjectTables(te.objects, tables)')
+        if objects is not None and te.objects is None:
+            raise ValueError('DeviceNavigator: object tables for a TeacherEpisode without objects')
         if mode not in MODES:
             raise ValueError('DeviceNavigator: mode is one of %s, got %r' % (sorted(MODES), mode))
         self.expert = getattr(te, 'expert_policy', 'spl')
@@ -153,42 +239,60 @@ class DeviceNavigator:
         if not (1 <= B <= MAX_B and 1 <= T <= MAX_T and 36 <= W <= MAX_W and 1 <= self.cap <= MAX_CAP and max(self.gw) <= MAX_G and min(self.gw) >= 2):
             raise ValueError('DeviceNavigator: B = %d, T = %d, W = %d, map widths %d..%d outside what goat_nav_step holds (B <= %d, T <= %d, '
                              '36 <= W <= %d, width <= %d)' % (B, T, W, min(self.gw), max(self.gw), MAX_B, MAX_T, MAX_W, min(MAX_G, MAX_CAP + 2)))
+        # object walks: O object slots behind the W views of every panorama, goals in a bucket of max_end end viewpoints
+        self.objects, self.max_end = objects, max_end
+        self.O = O = int(te.O) if objects is not None else 0
+        if objects is not None:
+            if objects.tables is not tables:
+                raise ValueError('DeviceNavigator: the object tables are numbered by another ScanTables')
+            if self.expert != 'spl':
+                raise ValueError('DeviceNavigator: the REVERIE / SOON agent has the shortest-path expert only')
+            if not (1 <= O <= MAX_O and 1 <= max_end <= MAX_END):
+                raise ValueError('DeviceNavigator: obj_width = %d, max_end = %d outside what goat_nav_obj_step holds (1..%d, 1..%d)'
+                                 % (O, max_end, MAX_O, MAX_END))
+        WT = self.WT = W + O
         C = self.A + 3
-        rows = lambda t: (t + 1) * (B * W + B) + (B if t > 0 else 0)
+        rows = lambda t: (t + 1) * (B * WT + B) + (B if t > 0 else 0)
         self._step_tensors = []
-        ptrs = []
+        ptrs, optrs = [], []
         for t in range(T):
             G, n = self.gw[t], rows(t)
-            want = {'feat_idx': (B * W,), 'feat_start': (B * W + 1,), 'loc_fts': (B, W, C), 'nav_types': (B, W), 'view_lens': (B,), 'gmap_step_ids': (B, G),
+            want = {'feat_idx': (B * W,), 'feat_start': (B * W + 1,), 'loc_fts': (B, WT, C), 'nav_types': (B, WT), 'view_lens': (B,), 'gmap_step_ids': (B, G),
                     'gmap_pos_fts': (B, G, C), 'gmap_pair_dists': (B, G, G), 'gmap_visited_masks': (B, G), 'gmap_masks': (B, G),
-                    'vp_pos_fts': (B, W + 2, 2 * C), 'vp_masks': (B, W + 2), 'vp_nav_masks': (B, W + 2), 'nav_fusion': (B, G, W + 2), 'target': (B,),
-                    'csr_idx': (n,), 'csr_start': (B * G + 1,), 'csr_scale': (B * G,), 'inv_idx': (n,), 'inv_start': (n + 1,), 'inv_w': (n,)}
+                    'vp_pos_fts': (B, WT + 2, 2 * C), 'vp_masks': (B, WT + 2), 'vp_nav_masks': (B, WT + 2), 'nav_fusion': (B, G, WT + 2), 'target': (B,),
+                    'csr_idx': (n,), 'csr_start': (B * G + 1,), 'csr_scale': (B * G,), 'inv_idx': (n,), 'inv_start': (n + 1,), 'inv_w': (n,),
+                    'obj_idx': (B * O,), 'obj_start': (B * O + 1,), 'reverie_obj_lens': (B,), 'reverie_obj_names': (B, O), 'vp_obj_masks': (B, WT + 2),
+                    'obj_target': (B,), 'ocat_idx': (B * WT,), 'ocat_start': (B * WT + 1,), 'ocat_inv_idx': (B * WT,),
+                    'ocat_inv_start': (B * W + B * O + 1,)}
             ts = []
-            for name, dtype in STEP_TABLES:
+            for name, dtype in STEP_TABLES + (OBJECT_STEP_TABLES if O else ()):
                 v = t_.get('s%d_%s' % (t, name))
                 if v is None or tuple(v.shape) != want[name] or v.dtype != dtype:
                     raise ValueError('DeviceNavigator: s%d_%s is %s, the navigator writes %s %s' % (
                         t, name, None if v is None else (tuple(v.shape), v.dtype), want[name], dtype))
                 ts.append(v)
             self._step_tensors.append(ts)
-            ptrs.append([v.data_ptr() for v in ts])
+            ptrs.append([v.data_ptr() for v in ts[:len(STEP_TABLES)]])
+            optrs.append([v.data_ptr() for v in ts[len(STEP_TABLES):]])
         h = _lib.lib()
-        self.state_ints, self.log_ints = h.goat_nav_state_ints(T, W, self.cap), h.goat_nav_log_ints(T, self.cap)
+        self.state_ints = h.goat_nav_obj_state_ints(T, W, O, self.cap) if O else h.goat_nav_state_ints(T, W, self.cap)
+        self.log_ints = h.goat_nav_log_ints(T, self.cap)
         if self.state_ints <= 0 or self.log_ints <= 0:
-            raise RuntimeError('libgoat_hip: goat_nav_state_ints(T=%d, W=%d, cap=%d) gave no size' % (T, W, self.cap))
+            raise RuntimeError('libgoat_hip: goat_nav_state_ints(T=%d, W=%d, O=%d, cap=%d) gave no size' % (T, W, O, self.cap))
         dev = self.device
         self.step_tab = torch.tensor(ptrs, dtype=torch.int64).to(dev)
+        self.ostep_tab = torch.tensor(optrs, dtype=torch.int64).to(dev) if O else None
         self.si = torch.zeros(B * self.state_ints, dtype=torch.int32, device=dev)
         self.sd = torch.zeros(B * (self.cap * self.cap + self.cap), dtype=torch.float64, device=dev)
         self.log = torch.zeros(2 * T * B + B * self.log_ints, dtype=torch.int32, device=dev)
-        self._live_at = 2 * (B + 1) + T * (B * W + B) + B
-        self.ws = torch.zeros(self._live_at + 1, dtype=torch.int32, device=dev)
+        self._live_at = 2 * (B + 1) + T * (B * WT + B) + B
+        self.ws = torch.zeros(self._live_at + 1 + (B + 1 if O else 0), dtype=torch.int32, device=dev)
         # staging of begin(): [u float64 [T, B] | ep int32 [B, 4] | forced actions int32 [T, B]] and, for the nDTW expert, behind them
-        # [ground-truth paths int32 [B, max_ref + 1]: length, viewpoint numbers]
+        # [ground-truth paths int32 [B, max_ref + 1]: length, viewpoint numbers]; for an object walk [goals int32 [B, max_end, 2]]
         self._n_u, self._n_ep = T * B * 8, B * 4 * 4
         self._n_forced = T * B * 4
         ndtw = self.expert == 'ndtw'
-        nbytes = self._n_u + self._n_ep + self._n_forced + (B * (max_ref + 1) * 4 if ndtw else 0)
+        nbytes = self._n_u + self._n_ep + self._n_forced + (B * (max_ref + 1) * 4 if ndtw else 0) + (B * max_end * 2 * 4 if O else 0)
         self._stage = torch.zeros(nbytes, dtype=torch.uint8)
         self._log_host = torch.zeros(self.log.numel(), dtype=torch.int32)
         if dev.type == 'cuda':
@@ -200,6 +304,8 @@ class DeviceNavigator:
         self._copied = None
         self.episodes = None
         self.launches_per_step = 2
+        if O:
+            self.goal = self._in[self._n_u + self._n_ep + self._n_forced:].view(torch.int32).view(B, max_end, 2)
         if ndtw:
             # the DTW row of the walked path and one working row per map node: sized by this navigator's cap and max_ref, not by the
             # limits of the ABI (there: 133 KB per episode)
@@ -244,6 +350,9 @@ class DeviceNavigator:
             for i, e in enumerate(episodes):
                 ref[i, 0] = len(e['path'])
                 ref[i, 1:1 + len(e['path'])] = [self.tables.vp(e['scan'].name, vp) for vp in e['path']]
+        if self.O:
+            goals = object_goals(episodes, self.objects, self.max_end, bool(getattr(te.sim, 'obj_fallback', False)))
+            st[self._n_u + self._n_ep + self._n_forced:].view(np.int32).reshape(B, self.max_end, 2)[:] = goals
         for i, e in enumerate(episodes):
             name = e['scan'].name
             ep[i] = (self.tables.ids[name], self.tables.vp(name, e['path'][0]), GraphSim._snap(e['heading'], 0.0), self.tables.vp(name, e['path'][-1]))
@@ -261,6 +370,10 @@ class DeviceNavigator:
             self._copied.record()
         self.episodes = list(episodes)
         self.host_s = time.perf_counter() - t0          # seconds of host work of this walk (packing here, the trajectories in finish())
+        if self.O:
+            launch('goat_nav_obj_reset', self.tables.tab, self.si, self.sd, self.log, self.ep, B, T, self.W, self.O, self.cap,
+                   what='goat_nav_obj_reset(B=%d,T=%d,O=%d,cap=%d)' % (B, T, self.O, self.cap))
+            return
         launch('goat_nav_reset', self.tables.tab, self.si, self.sd, self.log, self.ep, B, T, self.W, self.cap,
                what='goat_nav_reset(B=%d,T=%d,cap=%d)' % (B, T, self.cap))
 
@@ -272,9 +385,15 @@ class DeviceNavigator:
             act = self.forced
         if t > 0 and act is None:
             raise ValueError('DeviceNavigator.step(%d): the %s walk decides from the outputs of step %d' % (t, self.mode, t - 1))
-        launch('goat_nav_step', self.tables.tab, self.step_tab[t] if t < T else None, self.si, self.sd, self.log, self.ws,
-               act if t > 0 else None, self.u, MODES[self.mode], t, B, T, self.gw[t - 1] if t > 0 else 0, self.gw[t] if t < T else 0,
-               self.W, self.A, self.cap, int(self.te.ignoreid), what='goat_nav_step(t=%d,B=%d)' % (t, B))
+        if self.O:
+            launch('goat_nav_obj_step', self.tables.tab, self.objects.tab, self.step_tab[t] if t < T else None,
+                   self.ostep_tab[t] if t < T else None, self.si, self.sd, self.log, self.ws, act if t > 0 else None, self.u, self.goal,
+                   MODES[self.mode], t, B, T, self.gw[t - 1] if t > 0 else 0, self.gw[t] if t < T else 0, self.W, self.O, self.max_end,
+                   self.A, self.cap, int(self.te.ignoreid), what='goat_nav_obj_step(t=%d,B=%d)' % (t, B))
+        else:
+            launch('goat_nav_step', self.tables.tab, self.step_tab[t] if t < T else None, self.si, self.sd, self.log, self.ws,
+                   act if t > 0 else None, self.u, MODES[self.mode], t, B, T, self.gw[t - 1] if t > 0 else 0, self.gw[t] if t < T else 0,
+                   self.W, self.A, self.cap, int(self.te.ignoreid), what='goat_nav_step(t=%d,B=%d)' % (t, B))
         if t < T and self.expert == 'ndtw':
             launch('goat_nav_ndtw', self.tables.tab, self.step_tab[t], self.si, self.sd, self.log, self.ref, self.xd, t, B, T, self.W, self.cap,
                    self.max_ref, int(self.te.ignoreid), what='goat_nav_ndtw(t=%d,B=%d)' % (t, B))
@@ -306,6 +425,9 @@ class DeviceNavigator:
                 s = int(blocks[i, H_BT_START])
                 path.append([names[v] for v in hops[s:s + int(blocks[i, H_BT_N])]])
             traj.append({'instr_id': e['instr_id'], 'path': path})
+            if self.O and self.mode == 'argmax':        # EpisodePlanner(feedback='argmax'): the best object of the best stop node
+                v, j = int(blocks[i, H_PRED_VP]) - 1, int(blocks[i, H_PRED_OBJ])
+                traj[-1]['pred_objid'] = self.objects.ids[v][j] if (v >= 0 and j >= 0) else None
         actions = [acts[t].astype(np.int64) for t in range(T) if alive[t].any()]
         self.alive = alive.astype(bool)
         self.host_s += time.perf_counter() - t0

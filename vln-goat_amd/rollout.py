@@ -15,7 +15,7 @@ Here (M/ = /root/reference/map_nav_src), one module per layer, each importing on
                     public spelling of every class and function listed here.
   * episodes.py     planned episodes as shape-stable device work: `TeacherEpisode`, `EpisodePlanner`, `PlanWorker`, `EpisodeBuffers`.
   * sampled.py      sampled walks over captured graphs: `SampledEpisode`, `ArgmaxEpisode`, `SinglePassSampledEpisode`.
-  * navdev.py       the navigator of those walks on the device: `ScanTables`, `DeviceNavigator` (imports navsim.py, nav_inputs.py).
+  * navdev.py       the navigator of those walks on the device: `ScanTables`, `ObjectTables`, `DeviceNavigator` (imports navsim.py, nav_inputs.py).
 
   * `NavRollout`                  the rollout loop (M/r2r/agent.py:448-676) for feedback = teacher / argmax / sample.  Teacher
                                   forcing needs no device->host copy at all (the next action comes from the ground-truth path), so the
@@ -33,7 +33,7 @@ from .nav_inputs import (EXPERT_POLICIES, cal_dtw, language_inputs, panorama_inp
 from .episodes import (default_gmap_width, TeacherEpisode, _obj_concat_tables, EpisodePlanner, _RowIndex, _plan_worker_main,  # noqa: F401
                        PlanWorker, _pad1np, EpisodeBuffers)
 from .sampled import SampledEpisode, ArgmaxEpisode, SinglePassSampledEpisode  # noqa: F401
-from .navdev import ScanTables, DeviceNavigator  # noqa: F401
+from .navdev import ScanTables, ObjectTables, DeviceNavigator  # noqa: F401
 
 
 # ------------------------------------------------------------------------------------------------ the rollout (agent.py:448-676)
