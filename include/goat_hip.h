@@ -276,6 +276,48 @@ int goat_decode_select(void* stream, const float* logits, int64_t ld, int B, int
                        uint64_t seed, uint64_t offset, const uint64_t* rng_dev,
                        int32_t* pos_dev, int64_t* words, float* kmask, uint8_t* ended, int32_t* end_step, int32_t* n_live);
 
+/* Back-translation on the device (csrc/backtrans.hip): the self-training rollout of M/r2r/agent.py:457-474 (driven by
+ * M/r2r/main_nav.py:194-249 under --use_transpeaker) between the speaker's decode loop and the agent's walk.
+ *
+ * goat_retok_rows: decoded speaker words -> the agent's padded txt_ids / txt_masks rows; one workgroup per row, integers only.  What the
+ * reference does on the host per sentence: speaker.tok.shrink (M/utils/data.py:373-398), decode_sentence (:362-371), the agent's
+ * tokenizer on the joined string, `[:max_instr_len]` (M/r2r/agent.py:934) and the zero padding of _language_variable (:38-65).
+ *   words      int64 [B, ldw] (DecodeState.words: columns behind the newest word hold `pad`).
+ *   width      >= 2: that many columns of every row.  0: derived from the decode state as speaker.infer_batch_cached cuts its result,
+ *              *n_live > 0 ? *pos_dev + 1 : max_b(ended[b] ? end_step[b] : -1) + 2; every workgroup forms the maximum itself.  ended
+ *              uint8 [B], end_step int32 [B], pos_dev / n_live int32 [1] are read only then and may be NULL otherwise.
+ *   per row    (1) shrink: w[i] is kept for i < width - 1 where w[i] != w[i + 1] — the last column is always dropped, a run collapses to
+ *              its last element, a trailing run disappears; (2) end = index of the first `eos` among the kept words, or their number if
+ *              that index is 0 (none, or `eos` first); (3) start = 1 if more than one word is kept and the first is `bos`, else 0;
+ *              (4) the sentence is kept[start:end] up to the first `pad`; (5) word j expands to ids[start_tab[w] .. start_tab[w + 1]) of the
+ *              `first_*` table for the sentence-initial word and of the `rest_*` table for every later one (a byte-level BPE encodes
+ *              "walk" and " walk" differently; a word may expand to nothing); int32 CSR arrays, V + 1 starts each;
+ *              (6) out_ids[b] = ([agent_bos] + ids + [agent_eos])[:max_len], then fill_id up to ldo; out_mask[b, j] = j < lens[b] (one
+ *              byte per slot, the layout of a bool tensor); lens[b] = min(max_len, 2 + number of ids).
+ *   status     int32 [B], written by every launch: 0, or GOAT_RETOK_E_WIDTH (the width, given or derived, is < 2 or > ldw — the
+ *              reference raises on a one-column row), GOAT_RETOK_E_WORD (a word of the first `width` columns outside [0, V)),
+ *              GOAT_RETOK_E_EMPTY (the whole row is one run, nothing is kept: the reference's np.argmax raises on the empty list).  Such
+ *              a row gets lens 0, fill_id everywhere and a zero mask.
+ * GOAT_E_ARG: a null pointer (the four state pointers only with width == 0).  GOAT_E_SHAPE: ldw outside 1..512, width outside 0..512,
+ * max_len outside 2..512 or > ldo, B outside 1..1024, V < 1.  Both are returned before any launch. */
+#define GOAT_RETOK_E_WIDTH 1
+#define GOAT_RETOK_E_WORD 2
+#define GOAT_RETOK_E_EMPTY 4
+int goat_retok_rows(void* stream, const int64_t* words, int64_t ldw, const uint8_t* ended, const int32_t* end_step,
+                    const int32_t* pos_dev, const int32_t* n_live, int width, int B, int V, int bos, int eos, int pad,
+                    const int32_t* first_start, const int32_t* first_ids, const int32_t* rest_start, const int32_t* rest_ids,
+                    int agent_bos, int agent_eos, int64_t fill_id, int max_len, int64_t* out_ids, uint8_t* out_mask,
+                    int64_t ldo, int32_t* lens, int32_t* status);
+
+/* goat_scale_cols: out[r, c] = x[r, c] * noise[c] for c < D over `rows` rows of leading dimension ld (GOAT_F32 / GOAT_BF16; noise is
+ * float32 [D]): the shared environment-dropout mask `noise = drop_env(ones(feature_size))` of M/r2r/agent.py:459 multiplied into the
+ * image columns of the speaker's inputs (M/r2r/transpeaker.py:272-278) and into every view feature of the agent's panoramas
+ * (M/r2r/agent.py:86-148,541).  One float32 multiply per element, rounded once to the storage type.  Columns D..ld-1 are not touched
+ * when out == x and copied bit for bit otherwise.  16-byte chunks when x, out and noise are 16-byte aligned and ld is a multiple of the
+ * chunk (4 f32 / 8 bf16 elements), single elements otherwise; D needs no alignment.  x and out either coincide or do not overlap.
+ * GOAT_E_ARG: a null pointer, a bad dtype; GOAT_E_SHAPE: rows < 1, D < 1, ld < D, a base that is not element-aligned. */
+int goat_scale_cols(void* stream, int dtype, const void* x, void* out, const float* noise, int64_t rows, int64_t ld, int D);
+
 /* k-means over the pooled front-door features and the draw of the FACL dictionaries (csrc/kmeans.hip): what M/utils/data.py:403-480
  * (KMeansPicker: sklearn KMeans per modality, np.random.choice per cluster) does on the host.  Shared limits: X is [N, ld_x] in
  * GOAT_F32 or GOAT_BF16 with N >= 1, D a multiple of 8 (>= 8), ld_x >= D, 16-byte aligned rows; 1 <= K <= 256; C is float32 [K, D],

@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede CDLL, see module docstring)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 LIB_PATH = os.environ.get('GOAT_HIP_LIB') or os.path.join(CSRC, 'libgoat_hip.so')     # (override: kernel A/B experiments)
-SOURCES = ['gemm.hip', 'gemm2.hip', 'gemm3.hip', 'gemm5.hip', 'attention.hip', 'attention2.hip', 'attention_long.hip', 'decode.hip', 'kmeans.hip', 'zdict.hip', 'layernorm.hip', 'dropout_act.hip', 'linear_aux.hip', 'ce.hip', 'embed.hip', 'causal.hip', 'optim.hip', 'glue.hip', 'navmetrics.hip', 'valstats.hip', 'navstate.hip']
+SOURCES = ['gemm.hip', 'gemm2.hip', 'gemm3.hip', 'gemm5.hip', 'attention.hip', 'attention2.hip', 'attention_long.hip', 'decode.hip', 'backtrans.hip', 'kmeans.hip', 'zdict.hip', 'layernorm.hip', 'dropout_act.hip', 'linear_aux.hip', 'ce.hip', 'embed.hip', 'causal.hip', 'optim.hip', 'glue.hip', 'navmetrics.hip', 'valstats.hip', 'navstate.hip']
 
 GOAT_F32, GOAT_BF16 = 0, 1
 EPI_NONE, EPI_GELU, EPI_RELU, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_ACCUM = 0, 1, 2, 3, 4, 5
@@ -52,6 +52,9 @@ SIGNATURES = {
     'goat_attn_long_bwd': [_vp, _i32] + [_vp, _i64, _i64] * 8 + [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _u64, _u64, _vp],
     'goat_attn_decode_fwd': [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _f32, _u64, _u64, _vp],
     'goat_decode_select': [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'goat_retok_rows': [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _vp, _i64,
+                        _vp, _vp],
+    'goat_scale_cols': [_vp, _i32, _vp, _vp, _vp, _i64, _i64, _i32],
     'goat_kmeans_assign': [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32],
     'goat_kmeans_csr': [_vp, _vp, _vp, _vp, _i32, _i32],
     'goat_kmeans_centres': [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32],

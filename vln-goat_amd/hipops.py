@@ -16,6 +16,8 @@ Where things live (each module imports downward only; none imports this one):
   ops_embed      embedding (+ SparseEmbedGrad, check_embed_errors), pano_fusion, gather_segmean
   ops_heads      cross_entropy_rows, attn_pool, door_gate, dict_weighted_sum, sap_fuse, infonce, cfp_mix, cfp_tail, backward_mean;
                  val_rows, val_cfp, val_reduce (validation statistics, inference only)
+  ops_text       retok_rows (+ check_retok_status), scale_cols (back-translation: words to instruction rows, shared feature mask;
+                 inference only)
 and below them: _plumbing (pointers, launch), shadows (weight copies), gradsink (arena slices), tuning (GEMM configurations, AUTOTUNE,
 PROFILE), streams (graph capture, branches), wgrad_queue (deferred weight gradients and LayerNorm reductions).
 
@@ -49,6 +51,7 @@ from .ops_embed import (_EMBED_ERR, SparseEmbedGrad, _EmbedFn, _GatherFn, _PanoF
 from .ops_heads import (_MEAN_SEED, _AttnPoolFn, _CeRowsFn, _CfpMixFn, _CfpTailFn, _DictWsumFn, _DoorGateFn, _InfoNceFn, _SapFuseFn,      # noqa: F401
                         _cfp_mix_bwd, _cfp_mix_fwd, _u8, attn_pool, backward_mean, cfp_mix, cfp_tail, cross_entropy_rows, dict_weighted_sum,
                         door_gate, infonce, sap_fuse, val_cfp, val_reduce, val_rows)
+from .ops_text import RETOK_MAXB, RETOK_MAXL, RETOK_STATUS, check_retok_status, retok_rows, scale_cols      # noqa: F401
 
 
 class _HipopsModule(type(_sys)):

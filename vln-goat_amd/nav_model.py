@@ -257,7 +257,8 @@ _nav_fusion_matrix = nav_fusion_matrix
 
 
 class VLNBert(nn.Module):
-    """M/models/model.py:12-38: environment dropout on raw view features + mode dispatch."""
+    """M/models/model.py:12-38: environment dropout on raw view features + mode dispatch.  A panorama batch that carries `env_noise`
+    (float32 [D]) has its view features multiplied by it instead of dropped per element; the key is consumed here."""
 
     def __init__(self, args, config=None):
         super().__init__()
@@ -268,7 +269,12 @@ class VLNBert(nn.Module):
     def forward(self, mode, batch):
         batch = collections.defaultdict(lambda: None, batch)
         if mode == 'panorama':
-            if not batch['already_dropout']:
+            noise = batch.pop('env_noise', None)
+            if noise is not None:
+                # the shared mask of the back-translation rollout (M/r2r/agent.py:459,541: `already_dropout=True` features times one
+                # drop_env(ones(D)) per batch): float32 [D], read at launch time — a captured step sees the buffer's new contents
+                batch['view_img_fts'] = hipops.scale_cols(batch['view_img_fts'].to(compute_dtype()).contiguous(), noise)
+            elif not batch['already_dropout']:
                 batch['view_img_fts'] = hipops.dropout(batch['view_img_fts'].to(compute_dtype()).contiguous(), _p(self.drop_env))
             if 'reverie_obj_img_fts' in batch and batch['reverie_obj_img_fts'] is not None:
                 # object features are dropped regardless of `already_dropout` (M/models/model.py:31-32)

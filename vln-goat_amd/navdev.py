@@ -317,9 +317,13 @@ class DeviceNavigator:
             self.launches_per_step = 3
 
     # ---- one walk -------------------------------------------------------------------------------------------------------------
-    def begin(self, episodes, rng=None, actions=None):
+    def begin(self, episodes, rng=None, actions=None, text='host'):
         """start_walk for `episodes` ({instr_id, scan (ScanGraph), path, heading, instr_encoding}).  'sample': rng (numpy RandomState)
-        gives the uniforms; 'forced': actions [<= T, B] integers (missing steps are [stop], as TeacherEpisode.plan pads them)."""
+        gives the uniforms; 'forced': actions [<= T, B] integers (missing steps are [stop], as TeacherEpisode.plan pads them).
+        text='device': the instruction is what a kernel wrote into bufs.t['txt_ids'] / bufs.t['txt_masks'] already
+        (speaker.BackTranslator.run): nothing is packed or uploaded for it and `instr_encoding` is not read."""
+        if text not in ('host', 'device'):
+            raise ValueError("DeviceNavigator: text is 'host' or 'device', got %r" % (text,))
         te, B, T = self.te, self.B, self.T
         if len(episodes) != B:
             raise ValueError('DeviceNavigator: %d episodes for a state block of B = %d' % (len(episodes), B))
@@ -356,14 +360,15 @@ class DeviceNavigator:
         for i, e in enumerate(episodes):
             name = e['scan'].name
             ep[i] = (self.tables.ids[name], self.tables.vp(name, e['path'][0]), GraphSim._snap(e['heading'], 0.0), self.tables.vp(name, e['path'][-1]))
-        lang = language_inputs([{'instr_encoding': e['instr_encoding']} for e in episodes])
-        n = lang['txt_ids'].shape[1]
-        if n > te.L:
-            raise ValueError('instruction of %d tokens exceeds the text bucket %d' % (n, te.L))
-        ids = torch.zeros(B, te.L, dtype=torch.int64)
-        msk = torch.zeros(B, te.L, dtype=torch.bool)
-        ids[:, :n], msk[:, :n] = lang['txt_ids'], lang['txt_masks']
-        self.bufs.load_part({'txt_ids': ids, 'txt_masks': msk})
+        if text == 'host':
+            lang = language_inputs([{'instr_encoding': e['instr_encoding']} for e in episodes])
+            n = lang['txt_ids'].shape[1]
+            if n > te.L:
+                raise ValueError('instruction of %d tokens exceeds the text bucket %d' % (n, te.L))
+            ids = torch.zeros(B, te.L, dtype=torch.int64)
+            msk = torch.zeros(B, te.L, dtype=torch.bool)
+            ids[:, :n], msk[:, :n] = lang['txt_ids'], lang['txt_masks']
+            self.bufs.load_part({'txt_ids': ids, 'txt_masks': msk})
         self._in.copy_(self._stage, non_blocking=True)
         if self.device.type == 'cuda':
             self._copied = torch.cuda.Event()
@@ -433,13 +438,14 @@ class DeviceNavigator:
         self.host_s += time.perf_counter() - t0
         return traj, actions, int(blocks[:, H_LIVE].sum()), blocks[:, H_ENDED].astype(bool)
 
-    def walk(self, ep, episodes, rng=None, actions=None, act=None, after=None, check_every=None):
+    def walk(self, ep, episodes, rng=None, actions=None, act=None, after=None, check_every=None, text='host'):
         """the whole walk over the graphs of `ep` (g_lang, g_step): begin, per step the navigator then the step graph, the last move,
         `after()` (the backward graph of the single pass), the read-back.  act(t): the tensor step t + 1 decides from.
         check_every=k: before every k-th step graph the host reads the number of episodes still walking (one int; this synchronises) and
         leaves the loop at zero, as speaker.IncrementalDecoder does — for walks that end long before T and whose later step graphs
-        nobody needs (the validation walk; not the single pass, whose backward graph differentiates through every step)."""
-        self.begin(episodes, rng, actions)
+        nobody needs (the validation walk; not the single pass, whose backward graph differentiates through every step).
+        text: as begin()."""
+        self.begin(episodes, rng, actions, text)
         ep.g_lang.replay()
         done = False
         for t in range(self.T):

@@ -22,6 +22,7 @@ import torch
 from torch import nn
 
 from . import hipops
+from . import layers
 from .layers import compute_dtype, _p
 
 
@@ -434,6 +435,175 @@ def infer_batch_cached(model, can_feats, img_feats, bos, eos, pad, unk, max_deco
     st = dec.state
     n = max_decode + 1 if int(st.n_live.item()) else int(st.end_step.max().item()) + 2
     return st.words[:, :n].clone()
+
+
+# ------------------------------------------------------------------------------------------------ back-translation (M/r2r/agent.py:457-474)
+def shrink_words(row, bos, eos):
+    """`Tokenizer.shrink` (M/utils/data.py:373-398) on a plain list of word ids, quirks included:
+      * w[i] is kept only where w[i] != w[i + 1], for i < len - 1: the LAST column is always dropped, a run collapses to its last element
+        and a trailing run (the <PAD> tail, and a final <EOS> in front of nothing) disappears whole;
+      * end = index of the first <EOS> among the kept words — np.argmax of the comparison, which is 0 both when there is none and when
+        <EOS> comes first; either way end becomes the number of kept words ([<EOS>, a, b] keeps its <EOS>; a row without <EOS> loses
+        nothing but its last column);
+      * the first kept word is dropped if it is <BOS> and is not the only one ([<BOS>, <EOS>] decodes to '<BOS>').
+    An empty row comes back empty.  A row of one element, and a row that is one run of a single word, leave nothing to look for <EOS>
+    in: the reference's np.argmax raises ValueError there, and so does this."""
+    row = [int(w) for w in row]
+    if not row:
+        return row
+    kept = [row[i] for i in range(len(row) - 1) if row[i] != row[i + 1]]
+    if not kept:
+        raise ValueError('shrink_words: nothing is kept of a row of %d equal words (the reference raises: argmax of an empty sequence)' % len(row))
+    end = kept.index(eos) if eos in kept else 0
+    if end == 0:
+        end = len(kept)
+    start = 1 if (len(kept) > 1 and kept[0] == bos) else 0
+    return kept[start:end]
+
+
+def decode_words(row, pad):
+    """`Tokenizer.decode_sentence` (M/utils/data.py:362-371) without the join: the words up to the first <PAD>."""
+    out = []
+    for w in row:
+        if int(w) == pad:
+            break
+        out.append(int(w))
+    return out
+
+
+class RetokTable:
+    """The agent's tokenizer restricted to what the speaker can say: per speaker word the agent ids of the word at the start of a
+    sentence (`encode(w)`) and behind a space (`encode(' ' + w)`; a byte-level BPE tokenises "walk" and " walk" differently), as two CSR
+    tables of int32 device tensors: first_start / rest_start [V + 1], first_ids / rest_ids.  goat_retok_rows expands words through them.
+
+    It rests on one assumption: the tokenizer never merges across the single spaces `decode_sentence` joins the words with, so that a
+    sentence's tokenisation is the concatenation of its words'.  `check` verifies it for given sentences."""
+
+    def __init__(self, vocab_words, first, rest, device=None):
+        if len(first) != len(vocab_words) or len(rest) != len(vocab_words) or not vocab_words:
+            raise ValueError('RetokTable: one id list per vocabulary word and place')
+        self.vocab = list(vocab_words)
+        self.V = len(self.vocab)
+        self.first = [[int(i) for i in ids] for ids in first]
+        self.rest = [[int(i) for i in ids] for ids in rest]
+        if device is None:
+            device = 'cuda' if torch.cuda.is_available() else 'cpu'
+        for name, lists in (('first', self.first), ('rest', self.rest)):
+            start = np.zeros(self.V + 1, np.int64)
+            start[1:] = np.cumsum([len(ids) for ids in lists])
+            flat = np.asarray([i for ids in lists for i in ids] or [0], np.int64)      # (never empty: a pointer to hand to the kernel)
+            if start[-1] >= 2 ** 31 or flat.min() < -2 ** 31 or flat.max() >= 2 ** 31:
+                raise ValueError('RetokTable: ids and offsets are int32')
+            setattr(self, name + '_start', torch.from_numpy(start.astype(np.int32)).to(device))
+            setattr(self, name + '_ids', torch.from_numpy(flat.astype(np.int32)).to(device))
+
+    @classmethod
+    def build(cls, vocab_words, encode, device=None):
+        """vocab_words: the speaker vocabulary in id order, <BOS> included; encode: str -> list[int] WITHOUT special tokens (for the
+        reference's agent: lambda s: tok(s, add_special_tokens=False)['input_ids'])."""
+        return cls(vocab_words, [encode(w) for w in vocab_words], [encode(' ' + w) for w in vocab_words], device)
+
+    def host(self, words):
+        """the expansion goat_retok_rows makes, in Python: agent ids of the sentence `words` (speaker ids), no special tokens"""
+        out = []
+        for j, w in enumerate(words):
+            out += (self.first if j == 0 else self.rest)[int(w)]
+        return out
+
+    def sentence(self, words):
+        return ' '.join(self.vocab[int(w)] for w in words)
+
+    def instr_encoding(self, row, bos, eos, pad, agent_bos, agent_eos, max_len=None):
+        """a row of decoded words -> the `instr_encoding` the reference resets its environment with: shrink, decode_sentence, tokenise,
+        `[:max_len]` — a plain slice, which loses the </s> of a sentence that is too long (M/r2r/agent.py:934)."""
+        ids = [int(agent_bos)] + self.host(decode_words(shrink_words(row, bos, eos), pad)) + [int(agent_eos)]
+        return ids if max_len is None else ids[:max_len]
+
+    def check(self, encode, sentences):
+        """Raise ValueError when, for one of `sentences` (lists of speaker word ids), the tokenisation of the whole joined string is not
+        the concatenation of the table's per-word ids."""
+        for words in sentences:
+            text = self.sentence(words)
+            whole, parts = [int(i) for i in encode(text)], self.host(words)
+            if whole != parts:
+                raise ValueError('RetokTable: the tokenizer merges across words: %r encodes to %s, word by word to %s' % (text, whole, parts))
+
+
+class BackTranslator:
+    """Speaker words to agent instruction without leaving the device: what the reference's self-training rollout does between
+    `speaker.infer_batch` and `env.reset_epoch` (M/r2r/agent.py:457-474) — one shared environment-dropout mask on the speaker's image
+    features, greedy / sampled decoding, shrink + decode_sentence + the agent's tokenizer — with the KV-cached decoder and one
+    goat_retok_rows launch that writes the agent's `txt_ids` / `txt_masks` in place.
+
+        bt = BackTranslator(model, table, B, max_decode, T, bos, eos, pad, unk, agent_bos, agent_eos)
+        bt.draw_noise(vln_bert)                                        # noise = drop_env(ones(D)), in bt.noise
+        bt.run(can_feats, img_feats, bufs.t['txt_ids'], bufs.t['txt_masks'], noise=bt.noise)
+        nav.walk(ep, episodes, ..., text='device')                     # and extras={'panorama': {'env_noise': bt.noise}} in the body
+
+    run() makes no host read beyond the decoder's own n_live check; a row the reference would have raised on is recorded in
+    `status` and raised by check() / instr_encodings(), which synchronise."""
+
+    def __init__(self, model, table, B, max_decode, ctx_len, bos, eos, pad, unk, agent_bos, agent_eos, fill_id=0):
+        self.model, self.table = model, table
+        self.decoder = IncrementalDecoder(model, B, max_decode, ctx_len)
+        self.B, self.max_decode, self.ctx_len = int(B), int(max_decode), int(ctx_len)
+        self.bos, self.eos, self.pad, self.unk = int(bos), int(eos), int(pad), int(unk)
+        self.agent_bos, self.agent_eos, self.fill_id = int(agent_bos), int(agent_eos), int(fill_id)
+        if table.V != model.projection.weight.shape[0]:
+            raise ValueError('BackTranslator: the table holds %d words, the speaker projects onto %d' % (table.V, model.projection.weight.shape[0]))
+        dev = model.projection.weight.device
+        self.D = int(model.encoder.image_feat_size)
+        self.noise = torch.ones(self.D, dtype=torch.float32, device=dev)
+        self.lens = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.out_ids = None
+
+    @torch.no_grad()
+    def draw_noise(self, vln_bert):
+        """noise = vln_bert.drop_env(ones(D)) (M/r2r/agent.py:459) into the persistent buffer: all ones in eval mode."""
+        self.noise.copy_(hipops.dropout(torch.ones_like(self.noise), _p(vln_bert.drop_env)))
+        return self.noise
+
+    def _scaled(self, x, noise):
+        x = x.detach()
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        return hipops.scale_cols(x.contiguous(), noise)
+
+    @torch.no_grad()
+    def run(self, can_feats, img_feats, out_ids, out_masks, noise=None, sampling=False, check_every=8, max_len=None):
+        """can_feats [B, T, F], img_feats [B, T, 36, F] (speaker.path_features) -> the instruction rows in out_ids int64 / out_masks bool
+        [B, L] (e.g. the `txt_ids` / `txt_masks` of an EpisodeBuffers), at most max_len (default L) tokens each; -> lens int32 [B] on
+        the device.  noise: float32 [D] multiplied into the image columns of both inputs (transpeaker.py:272-278), the encoder then
+        skips its own feature dropout; None: the encoder drops per element as `infer_batch_cached` does."""
+        if noise is not None:
+            can_feats, img_feats = self._scaled(can_feats, noise), self._scaled(img_feats, noise)
+        enc_inputs, enc_outputs = self.model.encoder(can_feats, img_feats, noise is not None)
+        dec = self.decoder
+        dec.start(enc_outputs, self.bos, self.pad)
+        check_every = max(1, int(check_every))
+        for s in range(self.max_decode):
+            dec.step(self.unk, self.eos, self.pad, sampling)
+            if (s + 1) % check_every == 0 and s + 1 < self.max_decode and int(dec.state.n_live.item()) == 0:
+                break
+        hipops.retok_rows(dec.state.words, self.table, out_ids, out_masks, self.bos, self.eos, self.pad, self.agent_bos, self.agent_eos,
+                          self.fill_id, max_len, state=dec.state, lens=self.lens, status=self.status, check=False)
+        layers.refresh_masks(only=[out_masks, out_ids], force=True)      # (a raw kernel write bumps no version counter)
+        self.out_ids = out_ids
+        return self.lens
+
+    def check(self):
+        """raise ValueError for a row of the last run the reference would have raised on (reads the status back)"""
+        hipops.check_retok_status(self.status)
+
+    def instr_encodings(self):
+        """the instructions of the last run as lists of agent ids (`episodes[i]['instr_encoding']` of the host-planner forms); this is a
+        read-back."""
+        if self.out_ids is None:
+            raise RuntimeError('BackTranslator.instr_encodings: nothing has run')
+        self.check()
+        ids, lens = self.out_ids.cpu(), self.lens.cpu().tolist()
+        return [ids[i, :lens[i]].tolist() for i in range(self.B)]
 
 
 def path_features(sim, store, episodes, angle_size=128):
