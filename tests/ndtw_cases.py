@@ -1,41 +1,9 @@
-"""What the nDTW-expert tests share (test_ndtw_expert.py on the CPU, test_ndtw_expert_gpu.py on the device): the benches, a host walk of
-EpisodePlanner(expert_policy='ndtw') that records what the preconditions of the tests need, the table comparison of
-test_device_navigator_gpu.py, and the cases.  Nothing here needs a GPU."""
+"""What the nDTW-expert tests share beside the bench of nav_cases.py (test_ndtw_expert.py on the CPU, test_ndtw_expert_gpu.py on the
+device): the policies, what a host walk of EpisodePlanner(expert_policy='ndtw') records for the preconditions of the tests, and the
+cases.  Nothing here needs a GPU."""
 import numpy as np
-import torch
 
-A = 4
-TABLES = ('feat_idx', 'feat_start', 'loc_fts', 'nav_types', 'view_lens', 'gmap_step_ids', 'gmap_pos_fts', 'gmap_pair_dists', 'gmap_visited_masks',
-          'gmap_masks', 'vp_pos_fts', 'vp_masks', 'vp_nav_masks', 'nav_fusion', 'target', 'csr_idx', 'csr_start', 'csr_scale', 'inv_idx', 'inv_start',
-          'inv_w')
-# columns that go through sin / cos / asin (and the line distance): 1e-6; every other column exact (test_device_navigator_gpu.py)
-LOOSE = {'loc_fts': list(range(A)), 'gmap_pos_fts': list(range(A + 1)), 'vp_pos_fts': list(range(A + 1)) + [A + 3 + c for c in range(A + 1)]}
 MAX_REF = 12
-
-
-def bench(scans, T, gmap_width=None, expert_policy='ndtw'):
-    """sim over a key -> row index of `scans` and the episode bucket"""
-    from vln_goat_amd import rollout
-    keys = ['%s_%s' % (sc.name, vp) for sc in scans for vp in sc.vpids]
-    sim = rollout.GraphSim(rollout._RowIndex(keys))
-    kw = {} if gmap_width is None else {'gmap_width': gmap_width}
-    te = rollout.TeacherEpisode(sim, None, n_steps=T, text_len=32, pano_width=40, expert_policy=expert_policy, **kw)
-    return sim, te
-
-
-def random_policy(seed, p_stop):
-    rs = np.random.RandomState(seed)
-
-    def policy(t, p, part):
-        sel = (part['s%d_gmap_masks' % t] & ~part['s%d_gmap_visited_masks' % t]).numpy()
-        a = np.zeros(p.B, np.int64)
-        for b in range(p.B):
-            stop = rs.uniform() < p_stop
-            slots = np.nonzero(sel[b, 2:])[0] + 2
-            pick = int(slots[rs.randint(len(slots))]) if len(slots) else 0
-            a[b] = 0 if (stop or p.ended[b]) else pick
-        return a
-    return policy
 
 
 def frontier_policy(t, p, part):
@@ -92,50 +60,22 @@ def dtw_argmins(p):
     return out
 
 
-def host_walk(te, eps, policy):
-    """EpisodePlanner(te) driven by policy(t, planner, part) -> actions [B].  -> per-step tables, actions, the planner, and stats: labelled
-    states, states whose 'ndtw' and 'spl' labels differ, multi-hop moves, the longest shortest path to a candidate, states where the
-    order by -nDTW and the order by DTW disagree, the largest number of selectable unvisited nodes of a step."""
-    from vln_goat_amd import rollout
-    p = rollout.EpisodePlanner(te, eps, imitation=False)
-    parts, acts = [], []
-    stats = {'labelled': 0, 'differ': 0, 'multi': 0, 'max_hops': 0, 'exp_disagrees': 0, 'max_cands': 0}
-    for t in range(te.T):
-        part = {k: v.clone() for k, v in p.build_step().items()}
-        want = planner_labels(p, te.expert_policy)
-        assert np.array_equal(part['s%d_target' % t].numpy(), want)
-        spl = planner_labels(p, 'spl')
-        real = want >= 0
-        stats['labelled'] += int(real.sum())
-        stats['differ'] += int((want[real] != spl[real]).sum())
-        for n_best, d_best, hops in dtw_argmins(p):
-            stats['exp_disagrees'] += n_best != d_best
-            stats['max_hops'] = max([stats['max_hops']] + hops)
-            stats['max_cands'] = max(stats['max_cands'], len(hops))
-        a = policy(t, p, part)
-        before = [len(tr['path']) for tr in p.traj]
-        p.advance(a)
-        for tr, n in zip(p.traj, before):
-            stats['multi'] += sum(len(hop) > 1 for hop in tr['path'][n:n + 1])
-        parts.append(part)
-        acts.append(np.asarray(a, np.int64))
-    return parts, acts, p, stats
-
-
-def compare(t, got, want):
-    """every table of step t, padding included (got: {key: tensor} on any device)"""
-    for name in TABLES:
-        k = 's%d_%s' % (t, name)
-        g, w = got[k].cpu(), want[k]
-        assert g.shape == w.shape and g.dtype == w.dtype, k
-        if name in LOOSE:
-            loose = torch.zeros(g.shape[-1], dtype=torch.bool)
-            loose[LOOSE[name]] = True
-            assert torch.equal(g[..., ~loose], w[..., ~loose]), k
-            err = float((g[..., loose] - w[..., loose]).abs().max())
-            assert err <= 1e-6, (k, err)
-        else:
-            assert torch.equal(g, w), (k, g.reshape(-1)[:40], w.reshape(-1)[:40])
+def observe(t, p, part, stats):
+    """nav_cases.host_walk(observe=): the step's labels are teacher_action of the planner's expert on its own state; counts labelled
+    states, states whose 'ndtw' and 'spl' labels differ, the longest shortest path to a candidate, states where the order by -nDTW and
+    the order by DTW disagree, the largest number of selectable unvisited nodes of a step"""
+    for k in ('labelled', 'differ', 'max_hops', 'exp_disagrees', 'max_cands'):
+        stats.setdefault(k, 0)
+    want = planner_labels(p, p.te.expert_policy)
+    assert np.array_equal(part['s%d_target' % t].numpy(), want)
+    spl = planner_labels(p, 'spl')
+    real = want >= 0
+    stats['labelled'] += int(real.sum())
+    stats['differ'] += int((want[real] != spl[real]).sum())
+    for n_best, d_best, hops in dtw_argmins(p):
+        stats['exp_disagrees'] += n_best != d_best
+        stats['max_hops'] = max([stats['max_hops']] + hops)
+        stats['max_cands'] = max(stats['max_cands'], len(hops))
 
 
 def simple_path(scan, start, n):

@@ -1,23 +1,20 @@
-"""The device navigator without a GPU: goat_nav_reset / goat_nav_step reject null pointers and impossible sizes before any launch, and
+"""The device navigator without a GPU: goat_nav_reset / goat_nav_step reject null pointers and impossible sizes before any launch,
 navdev.ScanTables packs a scan exactly as the host navigator reads it (candidate order, pointId, angles, shortest distances, and the edge
-lengths GraphMap.update_graph would compute, bit for bit)."""
-import ctypes
-
+lengths GraphMap.update_graph would compute, bit for bit), navdev names the header words and lays out the workspace as the kernels do,
+and the kernels' text compiled as plain C++ (nav_cpu.py) samples its actions as SampledEpisode.sample does."""
 import numpy as np
 import pytest
 
+import nav_cases as N
+import nav_cpu
+
 E_ARG, E_SHAPE = -1, -2
-
-
-def _buf():
-    raw = (ctypes.c_char * 4096)()
-    return raw, ctypes.addressof(raw) & ~63
 
 
 def test_entry_points_reject_bad_arguments_before_any_launch():
     from vln_goat_amd import _lib
     h = _lib.lib()
-    raw, p = _buf()
+    raw, p = nav_cpu.buf()
     B, T, W, cap = 2, 3, 40, 14
     ok_reset = dict(scan_tab=p, si=p, sd=p, log=p, ep=p)
     for name in ok_reset:
@@ -82,3 +79,52 @@ def test_device_navigator_keeps_object_walks_on_the_host():
     te = type('TE', (), {'objects': object()})()
     with pytest.raises(NotImplementedError):
         rollout.DeviceNavigator(te, None, None, 'sample')
+
+
+# ---------------------------------------------------------------------------------------------------- the kernels' text on the CPU
+@pytest.fixture(scope='module')
+def cpu_kernel(tmp_path_factory):
+    return nav_cpu.build(tmp_path_factory.mktemp('navstate'))
+
+
+def test_navdev_names_the_header_words_and_lays_out_the_workspace_as_the_kernels_do(cpu_kernel):
+    from vln_goat_amd import navdev
+    h = cpu_kernel
+    assert navdev.HDR == h.cpu_header_ints() >= len(navdev.HEADER) == len(set(navdev.HEADER))
+    for i, name in enumerate(navdev.HEADER):
+        assert h.cpu_header_word(name.upper().encode()) == i == navdev.H[name], name
+    assert h.cpu_header_word(b'NO_SUCH_WORD') == -1
+    for B, T, W, O in ((1, 1, 1, 0), (5, 8, 40, 0), (6, 6, 40, 5), (12, 15, 40, 1), (1024, 64, 64, 0), (1024, 64, 64, 64)):
+        assert navdev.workspace(B, T, W, O) == (h.cpu_ws_ints(B, T, W, O), h.cpu_ws_live_at(B, T, W, O)), (B, T, W, O)
+
+
+SAMPLE_SEED = 0          # chosen on the host planner alone: a multi-hop move, and an episode still walking at T - 1
+
+
+def test_kernel_text_on_the_cpu_samples_as_the_host_planner_does(cpu_kernel):
+    """An R2R walk in 'sample' mode, B = 5, T = 8, over the two scans of ndtw_cases.case_two_scans: per step a seeded random float32
+    [B, G] with its mass on the selectable slots ([stop] scaled down so that walks last), uniforms from the same RandomState.  The host
+    planner moves by SampledEpisode.sample; the kernel text draws from the same probabilities with its own inverse CDF.  Step by step:
+    every table, the recorded action and the alive flag; at the end the ended flags and the number of live states."""
+    import ndtw_cases
+    from vln_goat_amd import rollout
+    from vln_goat_amd.navdev import H
+    scans, eps = ndtw_cases.case_two_scans()
+    B, T = len(eps), 8
+    sim, te = N.bench(scans, T)
+    rs = np.random.RandomState(SAMPLE_SEED)
+    u, probs, alive = rs.random_sample((T, B)), [], []
+
+    def policy(t, p, part):
+        sel = (part['s%d_gmap_masks' % t] & ~part['s%d_gmap_visited_masks' % t]).numpy()
+        pr = rs.random_sample(sel.shape).astype(np.float32) * sel
+        pr[:, 0] *= np.float32(0.05)
+        probs.append(pr)
+        alive.append(~p.ended)
+        return np.where(p.ended, 0, rollout.SampledEpisode.sample(pr, N.FixedRng(u[t])))
+    w = N.host_walk(te, eps, policy)
+    assert w.stats['multi'] >= 1 and not w.ended[T - 2].all(), (w.stats, w.ended[T - 2])
+    got = nav_cpu.cpu_walk(cpu_kernel, te, scans, eps, w, 'sample', probs=probs, u=u)
+    assert np.array_equal(got.acts, np.asarray(w.acts)) and np.array_equal(got.alive, np.asarray(alive))
+    assert N.check_sampling(probs, u, got.acts, got.alive) == int(np.sum(alive)) >= B + 1
+    assert np.array_equal(got.blocks[:, H['ended']].astype(bool), w.p.ended) and int(got.blocks[:, H['live']].sum()) == w.p.n_traj

@@ -11,120 +11,26 @@ import numpy as np
 import pytest
 import torch
 
+import nav_cases as N
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEV = 'cuda'
-A = 4
-TABLES = ('feat_idx', 'feat_start', 'loc_fts', 'nav_types', 'view_lens', 'gmap_step_ids', 'gmap_pos_fts', 'gmap_pair_dists', 'gmap_visited_masks',
-          'gmap_masks', 'vp_pos_fts', 'vp_masks', 'vp_nav_masks', 'nav_fusion', 'target', 'csr_idx', 'csr_start', 'csr_scale', 'inv_idx', 'inv_start',
-          'inv_w')
-# columns that go through sin / cos / asin (and the line distance): 1e-6; every other column exact
-LOOSE = {'loc_fts': list(range(A)), 'gmap_pos_fts': list(range(A + 1)), 'vp_pos_fts': list(range(A + 1)) + [A + 3 + c for c in range(A + 1)]}
 
 
-def _sync():
-    if DEV == 'cuda':
-        torch.cuda.synchronize()
-
-
-def _bench(scans, T, B_eps, gmap_width=None, feedback=None):
-    """sim over a key -> row index of `scans`, the episode bucket, the host planner factory"""
+def _navigator(te, scans, eps, sim, mode='forced'):
     from vln_goat_amd import rollout
-    keys = ['%s_%s' % (sc.name, vp) for sc in scans for vp in sc.vpids]
-    sim = rollout.GraphSim(rollout._RowIndex(keys))
-    kw = {} if gmap_width is None else {'gmap_width': gmap_width}
-    te = rollout.TeacherEpisode(sim, None, n_steps=T, text_len=32, pano_width=40, **kw)
-    return sim, te
-
-
-def _host_walk(te, eps, policy, feedback=None):
-    """the host planner driven by policy(t, planner, part) -> (actions [B], stop scores [B] | None) -> per-step tables, actions, scores,
-    ended flags after every move, the planner"""
-    from vln_goat_amd import rollout
-    p = rollout.EpisodePlanner(te, eps, imitation=False, feedback=feedback)
-    parts, acts, scores, ended, stats = [], [], [], [], {'multi': 0, 'moves': 0, 'noleft': 0, 'avg': 0, 'fusion_rows': 0}
-    for t in range(te.T):
-        part = {k: v.clone() for k, v in p.build_step().items()}
-        a, s = policy(t, p, part)
-        live = ~p.ended
-        stats['noleft'] += int(sum(bool(x) and l for x, l in zip(p._gin['no_vp_left'], live)))
-        stats['avg'] += int((part['s%d_csr_scale' % t] < 1).sum())
-        stats['fusion_rows'] += int(((part['s%d_nav_fusion' % t] > 0).sum(2) > 1).sum())
-        before = [len(tr['path']) for tr in p.traj]
-        if feedback == 'argmax':
-            p.advance(a, s, None)
-        else:
-            p.advance(a)
-        for tr, n in zip(p.traj, before):
-            for hop in tr['path'][n:n + 1]:
-                stats['moves'] += 1
-                stats['multi'] += len(hop) > 1
-        parts.append(part)
-        acts.append(np.asarray(a, np.int64))
-        scores.append(None if s is None else np.asarray(s, np.float32))
-        ended.append(p.ended.copy())
-    return parts, acts, scores, ended, p, stats
-
-
-def _random_policy(seed, p_stop):
-    rs = np.random.RandomState(seed)
-
-    def policy(t, p, part):
-        sel = (part['s%d_gmap_masks' % t] & ~part['s%d_gmap_visited_masks' % t]).numpy()
-        a = np.zeros(p.B, np.int64)
-        for b in range(p.B):
-            stop = rs.uniform() < p_stop
-            slots = np.nonzero(sel[b, 2:])[0] + 2
-            pick = int(slots[rs.randint(len(slots))]) if len(slots) else 0
-            a[b] = 0 if (stop or p.ended[b]) else pick
-        return a, rs.uniform(0.05, 0.95, p.B).astype(np.float32)
-    return policy
-
-
-def _compare(t, got, want):
-    for name in TABLES:
-        k = 's%d_%s' % (t, name)
-        g, w = got[k].cpu(), want[k]
-        assert g.shape == w.shape and g.dtype == w.dtype, k
-        if name in LOOSE:
-            loose = torch.zeros(g.shape[-1], dtype=torch.bool)
-            loose[LOOSE[name]] = True
-            assert torch.equal(g[..., ~loose], w[..., ~loose]), k
-            err = float((g[..., loose] - w[..., loose]).abs().max())
-            assert err <= 1e-6, (k, err)
-        else:
-            assert torch.equal(g, w), (k, g.reshape(-1)[:40], w.reshape(-1)[:40])
-
-
-def _device_forced(te, eps, tables, bufs, acts, parts, mode='forced', scores=None, nav=None):
-    """the navigator over `bufs` with the host's actions; every step's tables against `parts` -> (traj, actions, n_traj, ended)"""
-    from vln_goat_amd import rollout
-    nav = nav or rollout.DeviceNavigator(te, tables, bufs, mode)
-    back = torch.zeros(3, len(eps), dtype=torch.float32, device=DEV)
-    nav.begin(eps, actions=acts if mode == 'forced' else None)
-    for t in range(te.T + 1):
-        if t > 0 and mode == 'argmax':
-            back.copy_(torch.from_numpy(np.stack([acts[t - 1].astype(np.float32), scores[t - 1], np.zeros(len(eps), np.float32)])))
-        nav.step(t, back if mode == 'argmax' else None)
-        if t < te.T:
-            _sync()
-            _compare(t, bufs.t, parts[t])
-    return nav.finish()
+    bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
+    tables = rollout.ScanTables(scans, sim.features, device=DEV)
+    return rollout.DeviceNavigator(te, tables, bufs, mode), bufs
 
 
 def _parity(scans, eps, T, seed, p_stop, mode='forced', gmap_width=None):
-    from vln_goat_amd import rollout
-    feedback = 'argmax' if mode == 'argmax' else None
-    sim, te = _bench(scans, T, len(eps), gmap_width)
-    parts, acts, scores, ended, p, stats = _host_walk(te, eps, _random_policy(seed, p_stop), feedback)
-    bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
-    tables = rollout.ScanTables(scans, sim.features, device=DEV)
-    traj, actions, n_traj, dev_ended = _device_forced(te, eps, tables, bufs, acts, parts, mode, scores)
-    assert [tr['path'] for tr in traj] == [tr['path'] for tr in p.traj]
-    assert [tr['instr_id'] for tr in traj] == [tr['instr_id'] for tr in p.traj]
-    assert n_traj == p.n_traj
-    assert np.array_equal(dev_ended, p.ended)
-    return stats, ended, p, actions, acts
+    sim, te = N.bench(scans, T, gmap_width)
+    w = N.host_walk(te, eps, N.random_policy(seed, p_stop), 'argmax' if mode == 'argmax' else None)
+    nav, bufs = _navigator(te, scans, eps, sim, mode)
+    N.same_walk(N.device_walk(nav, eps, bufs, w, mode), w.p)
+    return w.stats, w.ended
 
 
 def _conditions(stats, ended, T, multi=True):
@@ -150,26 +56,22 @@ def _two_scans(n0, d0, n1, d1, B, T, seed):
 
 def test_case_a_fixture_actions():
     """A: synth.make_rollout_case() (24 nodes, B = 3, T = 5) under the sampled actions of the reference's own rollout."""
-    from vln_goat_amd import rollout, synth
+    from vln_goat_amd import synth
     z = np.load(os.path.join(HERE, 'golden', 'rollout_episode_sample.npz'))
     scan, _, eps, _ = synth.make_rollout_case()
     T = int(z['n_steps'][0])
-    sim, te = _bench([scan], T, len(eps))
-    fixed = lambda t, p, part: (np.where(p.ended, 0, z['s%d_action' % t]), None)
-    parts, acts, _, ended, p, stats = _host_walk(te, eps, fixed)
-    assert stats['avg'] >= 1 and not ended[T - 2].all()
-    bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
-    tables = rollout.ScanTables([scan], sim.features, device=DEV)
-    traj, actions, n_traj, dev_ended = _device_forced(te, eps, tables, bufs, acts, parts)
-    assert [tr['path'] for tr in traj] == [tr['path'] for tr in p.traj]
-    assert n_traj == p.n_traj and np.array_equal(dev_ended, p.ended)
+    sim, te = N.bench([scan], T)
+    w = N.host_walk(te, eps, lambda t, p, part: np.where(p.ended, 0, z['s%d_action' % t]))
+    assert w.stats['avg'] >= 1 and not w.ended[T - 2].all()
+    nav, bufs = _navigator(te, [scan], eps, sim)
+    N.same_walk(N.device_walk(nav, eps, bufs, w), w.p)
 
 
 def test_case_b_two_scans_in_one_batch():
     """B: scans of 24 (degree 3) and 29 (degree 2) nodes in one batch, B = 5, T = 8: multi-hop moves, averaged nodes, map rows with
     several fusion entries, ends forced at T - 1."""
     scans, eps = _two_scans(24, 3, 29, 2, 5, 8, seed=21)
-    stats, ended, p, _, _ = _parity(scans, eps, 8, seed=2, p_stop=0.05)
+    stats, ended = _parity(scans, eps, 8, seed=2, p_stop=0.05)
     _conditions(stats, ended, 8)
     assert stats['fusion_rows'] >= 1, stats
 
@@ -181,7 +83,7 @@ def test_case_c_argmax_stop_scores_and_backtrack():
     scan = rollout.ScanGraph.synthetic('scanC', n=4, seed=1, degree=1)
     T = 6
     eps = synth.rollout_episodes(scan, np.random.RandomState(3), B=2, max_steps=T, starts=[0, 2])
-    sim, te = _bench([scan], T, 2)
+    sim, te = N.bench([scan], T)
     tie = np.float32(0.5)
 
     def policy(t, p, part):
@@ -190,44 +92,22 @@ def test_case_c_argmax_stop_scores_and_backtrack():
         a0 = int(slots[0]) if len(slots) and not p.ended[0] else 0
         # episode 0: a tie between its first two nodes, lower scores behind them; episode 1 stops at once
         return np.array([a0, 0], np.int64), np.array([tie if t < 2 else 0.25, 0.75], np.float32)
-    parts, acts, scores, ended, p, stats = _host_walk(te, eps, policy, 'argmax')
-    assert stats['noleft'] >= 1 and ended[0][1] and not ended[0][0], (stats, ended)
+    w = N.host_walk(te, eps, policy, 'argmax')
+    p, ended = w.p, w.ended
+    assert w.stats['noleft'] >= 1 and ended[0][1] and not ended[0][0], (w.stats, ended)
     start0 = eps[0]['path'][0]
     assert p.traj[0]['path'][-1][-1] == start0 and len(p.traj[0]['path']) >= 3, p.traj[0]      # back to the FIRST of the tied nodes
-    bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
-    tables = rollout.ScanTables([scan], sim.features, device=DEV)
-    traj, actions, n_traj, dev_ended = _device_forced(te, eps, tables, bufs, acts, parts, 'argmax', scores)
-    assert [tr['path'] for tr in traj] == [tr['path'] for tr in p.traj]
-    assert n_traj == p.n_traj and np.array_equal(dev_ended, p.ended)
-    assert all(np.array_equal(x, y) for x, y in zip(actions, acts[:len(actions)]))
+    nav, bufs = _navigator(te, [scan], eps, sim, 'argmax')
+    got = N.device_walk(nav, eps, bufs, w, 'argmax')
+    N.same_walk(got, p)
+    assert all(np.array_equal(x, y) for x, y in zip(got[1], w.acts[:len(got[1])]))
 
 
 def test_case_d_full_bucket():
     """D: B = 12, T = 15 on scans of 40 and 45 nodes with the default 128-wide last bucket."""
     scans, eps = _two_scans(40, 3, 45, 3, 12, 15, seed=8)
-    stats, ended, p, _, _ = _parity(scans, eps, 15, seed=5, p_stop=0.05)
+    stats, ended = _parity(scans, eps, 15, seed=5, p_stop=0.05)
     _conditions(stats, ended, 15)
-
-
-class _FixedRng:
-    def __init__(self, u):
-        self.u = u
-
-    def random_sample(self, n):
-        return self.u
-
-
-def _check_sampling(nav, probs, u, actions, alive):
-    """the recorded action of every live episode equals SampledEpisode.sample on the host from the same probs and uniform"""
-    from vln_goat_amd import rollout
-    n = 0
-    for t in range(len(probs)):
-        want = rollout.SampledEpisode.sample(probs[t], _FixedRng(u[t]))
-        for b in range(probs[t].shape[0]):
-            if alive[t, b]:
-                assert actions[t][b] == want[b], (t, b, actions[t][b], want[b])
-                n += 1
-    return n
 
 
 def test_sampling_is_the_hosts():
@@ -237,15 +117,13 @@ def test_sampling_is_the_hosts():
     scan = rollout.ScanGraph.synthetic('scanS', n=24, seed=9, degree=3)
     T, B = 4, 4
     eps = synth.rollout_episodes(scan, np.random.RandomState(1), B=B, max_steps=T, starts=[0, 5, 9, 14])
-    sim, te = _bench([scan], T, B)
-    bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
-    tables = rollout.ScanTables([scan], sim.features, device=DEV)
-    nav = rollout.DeviceNavigator(te, tables, bufs, 'sample')
+    sim, te = N.bench([scan], T)
+    nav, bufs = _navigator(te, [scan], eps, sim, 'sample')
     rs = np.random.RandomState(4)
     u = rs.random_sample((T, B))
     u[:, 1] = 1.0 - 2.0 ** -53          # the largest double below 1
     u[0, 2] = 0.0
-    nav.begin(eps, _FixedRng(u))
+    nav.begin(eps, N.FixedRng(u))
     probs = []
     for t in range(T + 1):
         if t > 0:
@@ -262,10 +140,10 @@ def test_sampling_is_the_hosts():
             nav.step(t, torch.from_numpy(p).to(DEV))
         else:
             nav.step(0)
-        _sync()
+        torch.cuda.synchronize()
     traj, actions, n_traj, ended = nav.finish()
     assert len(actions) == T
-    assert _check_sampling(nav, probs, u, actions, nav.alive) >= B * (T - 1)
+    assert N.check_sampling(probs, u, actions, nav.alive) >= B * (T - 1)
     for t in range(T - 1):                  # no padding slot, no visited node was drawn: the walk took a hop at every step but the last
         assert all(len(tr['path']) == T for tr in traj), [len(tr['path']) for tr in traj]
 
@@ -281,11 +159,10 @@ def _status_bench():
 def test_status_words_raise_and_the_process_stays_usable():
     from vln_goat_amd import rollout
     scan, T, B, eps = _status_bench()
-    sim, te = _bench([scan], T, B)
-    parts, acts, _, _, p, _ = _host_walk(te, eps, _random_policy(3, 0.0))
-    bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
-    tables = rollout.ScanTables([scan], sim.features, device=DEV)
-    nav = rollout.DeviceNavigator(te, tables, bufs, 'forced')
+    sim, te = N.bench([scan], T)
+    w = N.host_walk(te, eps, N.random_policy(3, 0.0))
+    acts, p = w.acts, w.p
+    nav, bufs = _navigator(te, [scan], eps, sim)
     bad = [a.copy() for a in acts]
     bad[1][1] = 2                       # slot 2 of step 1 is the start node: visited
     nav.begin(eps, actions=bad)
@@ -293,36 +170,30 @@ def test_status_words_raise_and_the_process_stays_usable():
         nav.step(t)
     with pytest.raises(ValueError, match=r'episode 1, step 1'):
         nav.finish()
-    traj, _, n_traj, _ = _device_forced(te, eps, tables, bufs, acts, parts, nav=nav)       # a second, valid walk over the same state block
+    traj, _, n_traj, _ = N.device_walk(nav, eps, bufs, w)       # a second, valid walk over the same state block
     assert [tr['path'] for tr in traj] == [tr['path'] for tr in p.traj] and n_traj == p.n_traj
     # a bucket narrower than the map
     # (buffers of that width from a 4-node scan, whose maps fit; the 24-node scan's do not)
     from vln_goat_amd import synth
     small = rollout.ScanGraph.synthetic('scanC', n=4, seed=1, degree=1)
     eps4 = synth.rollout_episodes(small, np.random.RandomState(3), B=B, max_steps=T, starts=[0, 2])
-    sim8, te8 = _bench([scan, small], T, B, gmap_width=lambda t: 8)
-    bufs8 = rollout.EpisodeBuffers(te8.plan(eps4), device=DEV)
-    tables8 = rollout.ScanTables([scan, small], sim8.features, device=DEV)
-    nav8 = rollout.DeviceNavigator(te8, tables8, bufs8, 'forced')
+    sim8, te8 = N.bench([scan, small], T, gmap_width=lambda t: 8)
+    nav8, bufs8 = _navigator(te8, [scan, small], eps4, sim8)
     nav8.begin(eps, actions=acts)
     for t in range(T + 1):
         nav8.step(t)
     with pytest.raises(ValueError, match=r'episode \d, step \d.*map'):
         nav8.finish()
-    parts4, acts4, _, _, p4, _ = _host_walk(te8, eps4, _random_policy(4, 0.0))
-    traj, _, n_traj, _ = _device_forced(te8, eps4, tables8, bufs8, acts4, parts4, nav=nav8)
+    w4 = N.host_walk(te8, eps4, N.random_policy(4, 0.0))
+    p4 = w4.p
+    traj, _, n_traj, _ = N.device_walk(nav8, eps4, bufs8, w4)
     assert [tr['path'] for tr in traj] == [tr['path'] for tr in p4.traj] and n_traj == p4.n_traj
 
 
 # ---------------------------------------------------------------------------------------------------- with the model (E, F, masks)
-EP_ARGS = dict(num_l_layers=2, num_x_layers=2, num_pano_layers=2, dropout=0.5, feat_dropout=0.4, do_back_img=True, do_back_txt=True,
-               do_front_img=True, do_front_his=True, do_front_txt=True, vocab_size=1200, mode='train', do_back_txt_type='type_2',
-               do_back_img_type='type_1', do_add_method='door')
-
-
 def _model():
     from vln_goat_amd import nav_model, synth
-    cfg = nav_model.nav_config_from_args(SimpleNamespace(**EP_ARGS))
+    cfg = nav_model.nav_config_from_args(SimpleNamespace(**N.EP_ARGS))
     torch.manual_seed(0)
     m = nav_model.GlocalTextPathNavCMT(cfg)
     m.load_state_dict(synth.seeded_state_dict(m, seed=11))
@@ -332,18 +203,6 @@ def _model():
 def _store(scan, feats, dtype):
     from vln_goat_amd import features
     return features.FeatureStore.from_arrays({'%s_%s' % (scan.name, vp): feats[i] for i, vp in enumerate(scan.vpids)}, dtype=dtype).to('cuda')
-
-
-def _masks_match():
-    """every memoised mask equals its recomputation from the table it was derived from"""
-    from vln_goat_amd import layers
-    n = 0
-    for ent in layers._MASK_MEMO.values():
-        src = ent[0]()
-        if src is not None:
-            assert torch.equal(ent[2], ent[3](src)), ent[2].shape
-            n += 1
-    return n
 
 
 def test_e_single_pass_end_to_end_and_mask_memo():
@@ -379,9 +238,9 @@ def test_e_single_pass_end_to_end_and_mask_memo():
         u = np.random.RandomState(100 + rnd).random_sample((T, len(eps)))
         traj, actions = sp.run(episodes, np.random.RandomState(100 + rnd), navigator=nav)
         torch.cuda.synchronize()
-        assert _masks_match() > 0
+        assert N.masks_match() > 0
         probs = [pr.float().cpu().numpy() for pr in sp.probs]
-        assert _check_sampling(nav, probs, u, [a for a in actions] + [None] * (T - len(actions)), nav.alive) >= len(eps)
+        assert N.check_sampling(probs, u, [a for a in actions] + [None] * (T - len(actions)), nav.alive) >= len(eps)
         loss = float(sp.loss)
         grads = {id(p): (None if p.grad is None else p.grad.detach().clone()) for p in params}
         n_traj = sp.n_traj
@@ -425,7 +284,7 @@ def test_f_argmax_walk_end_to_end():
     for episodes in (eps, other, eps):
         traj = walk.run(episodes, navigator=nav)
         actions = [a.copy() for a in walk.actions]
-        assert _masks_match() > 0
+        assert N.masks_match() > 0
         scores = nav.sd.view(len(eps), -1)[:, nav.cap * nav.cap:].cpu().numpy()
         early = walk.run(episodes, navigator=nav, check_every=1)          # the host stops replaying once nobody walks
         assert [tr['path'] for tr in early] == [tr['path'] for tr in traj]

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import nav_cases as N
 import ndtw_cases as C
 
 pytestmark = pytest.mark.gpu
@@ -18,81 +19,58 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DEV = 'cuda'
 
 
-def _device_forced(te, eps, nav, bufs, acts, parts):
-    """the navigator over `bufs` with the host's actions; every step's tables against `parts` -> (traj, actions, n_traj, ended)"""
-    nav.begin(eps, actions=acts)
-    for t in range(te.T + 1):
-        nav.step(t)
-        if t < te.T:
-            torch.cuda.synchronize()
-            C.compare(t, bufs.t, parts[t])
-    return nav.finish()
-
-
-def _walks_match(got, p):
-    traj, actions, n_traj, ended = got
-    assert [tr['path'] for tr in traj] == [tr['path'] for tr in p.traj]
-    assert [tr['instr_id'] for tr in traj] == [tr['instr_id'] for tr in p.traj]
-    assert n_traj == p.n_traj and np.array_equal(ended, p.ended)
-
-
 def _parity(scans, eps, T, policy, max_ref, gmap_width=None):
     from vln_goat_amd import rollout
-    sim, te = C.bench(scans, T, gmap_width)
-    parts, acts, p, stats = C.host_walk(te, eps, policy)
+    sim, te = N.bench(scans, T, gmap_width, expert_policy='ndtw')
+    w = N.host_walk(te, eps, policy, observe=C.observe)
     bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
     tables = rollout.ScanTables(scans, sim.features, device=DEV)
     nav = rollout.DeviceNavigator(te, tables, bufs, 'forced', max_ref=max_ref)
     assert nav.launches_per_step == 3
-    return stats, te, nav, bufs, tables, parts, acts, p
+    return te, nav, bufs, w
 
 
 def test_1_step_by_step_parity_two_scans():
     """scans of 24 (degree 3) and 29 (degree 2) nodes in one batch, B = 5, T = 8, forced mode under the host's random policy; ground-truth
     paths of exactly max_ref = 12, of 1 (start = goal) and of 2 viewpoints among them"""
     scans, eps = C.case_two_scans()
-    stats, te, nav, bufs, _, parts, acts, p = _parity(scans, eps, 8, C.random_policy(2, 0.05), C.MAX_REF)
-    C.preconditions(stats)
-    _walks_match(_device_forced(te, eps, nav, bufs, acts, parts), p)
+    te, nav, bufs, w = _parity(scans, eps, 8, N.random_policy(2, 0.05, scores=False), C.MAX_REF)
+    C.preconditions(w.stats)
+    N.same_walk(N.device_walk(nav, eps, bufs, w), w.p)
 
 
 def test_2_more_candidates_than_a_wavefront():
     """one scan of 120 nodes, degree 6, B = 2, T = 20, the map bucket 128 wide: a step with more than 64 selectable unvisited nodes"""
     scans, eps = C.case_wide()
-    stats, te, nav, bufs, _, parts, acts, p = _parity(scans, eps, 20, C.frontier_policy, 24, gmap_width=lambda t: 128)
-    C.preconditions(stats)
-    assert stats['max_cands'] > 64, stats
-    _walks_match(_device_forced(te, eps, nav, bufs, acts, parts), p)
+    te, nav, bufs, w = _parity(scans, eps, 20, C.frontier_policy, 24, gmap_width=lambda t: 128)
+    C.preconditions(w.stats)
+    assert w.stats['max_cands'] > 64, w.stats
+    N.same_walk(N.device_walk(nav, eps, bufs, w), w.p)
 
 
 def test_3_one_navigator_walks_two_batches():
     """the DTW row and the fold counter of the first walk do not leak into the second"""
     from vln_goat_amd import synth
     scans, eps = C.case_two_scans()
-    stats, te, nav, bufs, _, parts, acts, p = _parity(scans, eps, 8, C.random_policy(2, 0.05), C.MAX_REF)
-    _walks_match(_device_forced(te, eps, nav, bufs, acts, parts), p)
+    te, nav, bufs, w = _parity(scans, eps, 8, N.random_policy(2, 0.05, scores=False), C.MAX_REF)
+    N.same_walk(N.device_walk(nav, eps, bufs, w), w.p)
     rs = np.random.RandomState(77)
     e0 = synth.rxr_episodes(scans[0], rs, B=3, max_ref=C.MAX_REF, starts=[4, 13, 20])
     e1 = synth.rxr_episodes(scans[1], rs, B=2, max_ref=C.MAX_REF, starts=[5, 17])
     other = [e1[0], e0[0], e1[1], e0[1], e0[2]]
     for i, e in enumerate(other):
         e['instr_id'] = 'other%d' % i
-    parts2, acts2, p2, stats2 = C.host_walk(te, other, C.random_policy(9, 0.05))
-    C.preconditions(stats2)
-    _walks_match(_device_forced(te, other, nav, bufs, acts2, parts2), p2)
+    w2 = N.host_walk(te, other, N.random_policy(9, 0.05, scores=False), observe=C.observe)
+    C.preconditions(w2.stats)
+    N.same_walk(N.device_walk(nav, other, bufs, w2), w2.p)
     too_long = [dict(e) for e in other]
     too_long[3]['path'] = C.simple_path(scans[0], 0, C.MAX_REF + 1)
     with pytest.raises(ValueError, match='episode 3.*13 viewpoints'):
-        nav.begin(too_long, actions=acts2)
-    _walks_match(_device_forced(te, eps, nav, bufs, acts, parts), p)             # the refused batch launched nothing
+        nav.begin(too_long, actions=w2.acts)
+    N.same_walk(N.device_walk(nav, eps, bufs, w), w.p)             # the refused batch launched nothing
 
 
 # ---------------------------------------------------------------------------------------------------- with the model
-EP_ARGS = dict(num_l_layers=2, num_x_layers=2, num_pano_layers=2, dropout=0.5, feat_dropout=0.4, do_back_img=True, do_back_txt=True,
-               do_front_img=True, do_front_his=True, do_front_txt=True, vocab_size=1200, mode='train', do_back_txt_type='type_2',
-               do_back_img_type='type_1', do_add_method='door')
-
-
 def test_4_single_pass_end_to_end():
     """SinglePassSampledEpisode.run(navigator=) with the 'ndtw' navigator against the same object on the host planner
     (expert_policy='ndtw') under the same rng: equal actions and trajectories, the loss to 2e-5 (the bound
@@ -102,7 +80,7 @@ def test_4_single_pass_end_to_end():
     T, B = 5, 3
     eps = synth.rxr_episodes(scan, np.random.RandomState(7), B=B, max_ref=C.MAX_REF)      # (the experts disagree at step 0 already)
     torch.manual_seed(0)
-    model = nav_model.GlocalTextPathNavCMT(nav_model.nav_config_from_args(SimpleNamespace(**EP_ARGS)))
+    model = nav_model.GlocalTextPathNavCMT(nav_model.nav_config_from_args(SimpleNamespace(**N.EP_ARGS)))
     model.load_state_dict(synth.seeded_state_dict(model, seed=11))
     model = model.cuda().eval()
     store = features.FeatureStore.from_arrays({'%s_%s' % (scan.name, vp): feats[i] for i, vp in enumerate(scan.vpids)}, dtype=torch.float32).to('cuda')
@@ -140,7 +118,7 @@ def test_4_single_pass_end_to_end():
 def test_5_spl_navigator_keeps_its_two_launches():
     from vln_goat_amd import rollout
     scans, eps = C.case_two_scans()
-    sim, te = C.bench(scans, 4, expert_policy='spl')
+    sim, te = N.bench(scans, 4, expert_policy='spl')
     bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
     tables = rollout.ScanTables(scans, sim.features, device=DEV)
     nav = rollout.DeviceNavigator(te, tables, bufs, 'forced')

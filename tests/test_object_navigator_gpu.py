@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import nav_cases as N
 import object_nav_cases as C
 
 pytestmark = pytest.mark.gpu
@@ -23,8 +24,8 @@ def case():
     scans, objects = C.scans_and_objects()
     eps = C.episodes(scans, objects)
     sim, te = C.bench(scans, objects)
-    forced = C.host_walk(te, eps, C.policy(2))
-    argmax = C.host_walk(te, eps, C.policy(2, tie=(1, (0, 1), 0.5)), feedback='argmax')
+    forced = N.host_walk(te, eps, C.policy(2), observe=C.observe)
+    argmax = N.host_walk(te, eps, C.policy(2, tie=(1, (0, 1), 0.5)), 'argmax', C.observe)
     bufs = rollout.EpisodeBuffers(te.plan(eps), device=DEV)
     tables = rollout.ScanTables(scans, sim.features, device=DEV)
     ot = rollout.ObjectTables(objects, tables, device=DEV)
@@ -33,24 +34,12 @@ def case():
 
 def _device_walk(te, eps, bufs, nav, mode, walk):
     """the navigator over `bufs` under the host walk's actions (and stop scores / best objects); every step's tables against the host's"""
-    parts, acts, scores, bests = walk[:4]
-    back = torch.zeros(3, len(eps), dtype=torch.float32, device=DEV)
-    nav.begin(eps, actions=acts if mode == 'forced' else None)
-    for t in range(te.T + 1):
-        if t > 0 and mode == 'argmax':
-            back.copy_(torch.from_numpy(np.stack([acts[t - 1].astype(np.float32), scores[t - 1], bests[t - 1]])))
-        nav.step(t, back if mode == 'argmax' else None)
-        if t < te.T:
-            torch.cuda.synchronize()
-            C.compare(t, bufs.t, parts[t])
-    return nav.finish()
+    return N.device_walk(nav, eps, bufs, walk, mode, N.TABLES + N.OBJECT_TABLES)
 
 
 def _same_walk(got, p, argmax):
-    traj, actions, n_traj, ended = got
-    assert [tr['path'] for tr in traj] == [tr['path'] for tr in p.traj]
-    assert [tr['instr_id'] for tr in traj] == [tr['instr_id'] for tr in p.traj]
-    assert n_traj == p.n_traj and np.array_equal(ended, p.ended)
+    N.same_walk(got, p)
+    traj = got[0]
     if argmax:
         assert [tr['pred_objid'] for tr in traj] == [tr['pred_objid'] for tr in p.traj]
     else:
@@ -60,16 +49,17 @@ def _same_walk(got, p, argmax):
 def test_forced_walk_builds_every_table_of_the_host_planner(case):
     from vln_goat_amd import rollout
     c = case
-    C.preconditions(c['forced'][6], c['forced'][4])
+    C.preconditions(c['forced'].stats, c['forced'].ended)
     nav = rollout.DeviceNavigator(c['te'], c['tables'], c['bufs'], 'forced', objects=c['ot'], max_end=4)
     assert nav.launches_per_step == 2
-    _same_walk(_device_walk(c['te'], c['eps'], c['bufs'], nav, 'forced', c['forced']), c['forced'][5], False)
+    _same_walk(_device_walk(c['te'], c['eps'], c['bufs'], nav, 'forced', c['forced']), c['forced'].p, False)
 
 
 def test_argmax_walk_records_the_best_objects_and_backtracks(case):
     from vln_goat_amd import rollout
     c = case
-    parts, acts, scores, bests, ended, p, stats = c['argmax']
+    w = c['argmax']
+    parts, scores, bests, ended, p, stats = w.parts, w.scores, w.bests, w.ended, w.p, w.stats
     C.preconditions(stats, ended)
     # row 2 is negative wherever the viewpoint has no objects; episode 1 is scored twice with the same value on two viewpoints
     for t in range(c['te'].T):
@@ -87,13 +77,13 @@ def test_a_second_walk_over_the_same_state_block_keeps_nothing_of_the_first(case
     c = case
     te = c['te']
     nav = rollout.DeviceNavigator(te, c['tables'], c['bufs'], 'argmax', objects=c['ot'], max_end=4)
-    _same_walk(_device_walk(te, c['eps'], c['bufs'], nav, 'argmax', c['argmax']), c['argmax'][5], True)
+    _same_walk(_device_walk(te, c['eps'], c['bufs'], nav, 'argmax', c['argmax']), c['argmax'].p, True)
     other = list(reversed(C.episodes(c['scans'], c['objects'], seed=5, absent=1)))
     for i, e in enumerate(other):
         e['instr_id'] = 'other%d' % i
-    walk = C.host_walk(te, other, C.policy(7), feedback='argmax')
-    assert [tr['pred_objid'] for tr in walk[5].traj] != [tr['pred_objid'] for tr in c['argmax'][5].traj]
-    _same_walk(_device_walk(te, other, c['bufs'], nav, 'argmax', walk), walk[5], True)
+    walk = N.host_walk(te, other, C.policy(7), 'argmax', C.observe)
+    assert [tr['pred_objid'] for tr in walk.p.traj] != [tr['pred_objid'] for tr in c['argmax'].p.traj]
+    _same_walk(_device_walk(te, other, c['bufs'], nav, 'argmax', walk), walk.p, True)
     goals = nav.goal.cpu().numpy()
     from vln_goat_amd import navdev
     assert np.array_equal(goals, navdev.object_goals(other, c['ot'], 4))
@@ -112,31 +102,19 @@ def test_a_viewpoint_with_more_objects_than_the_bucket_is_a_status_word(case):
                         'obj_id': ot.ids[tables.vp(sc.name, vp)][0] if count[vp] else None}
     ok, bad = [ep(0, few), ep(1, none)], [ep(0, few), ep(1, many)]
     sim, te = C.bench(scans, objects, T=2, obj_width=3)
-    walk = C.host_walk(te, ok, C.policy(1))
-    assert walk[6]['labelled'] >= 1
+    walk = N.host_walk(te, ok, C.policy(1), observe=C.observe)
+    assert walk.stats['labelled'] >= 1
     bufs = rollout.EpisodeBuffers(te.plan(ok), device=DEV)
     nav = rollout.DeviceNavigator(te, tables, bufs, 'forced', objects=ot, max_end=2)
-    nav.begin(bad, actions=walk[1])
+    nav.begin(bad, actions=walk.acts)
     for t in range(te.T + 1):
         nav.step(t)
     with pytest.raises(ValueError, match=r'episode 1, step 0.*objects'):
         nav.finish()
-    _same_walk(_device_walk(te, ok, bufs, nav, 'forced', walk), walk[5], False)
+    _same_walk(_device_walk(te, ok, bufs, nav, 'forced', walk), walk.p, False)
 
 
 # ---------------------------------------------------------------------------------------------------- with the model
-def _masks_match():
-    """every memoised mask equals its recomputation from the table it was derived from"""
-    from vln_goat_amd import layers
-    n = 0
-    for ent in layers._MASK_MEMO.values():
-        src = ent[0]()
-        if src is not None:
-            assert torch.equal(ent[2], ent[3](src)), ent[2].shape
-            n += 1
-    return n
-
-
 def test_argmax_episode_runs_on_the_object_navigator():
     """ArgmaxEpisode.run(navigator=) on synth.make_reverie_rollout_case() with the model of test_argmax_walk_gpu.py's reverie case: paths,
     pred_objid and recorded actions equal walk.run(episodes) on the host planner, also with check_every=1"""
@@ -152,7 +130,7 @@ def test_argmax_episode_runs_on_the_object_navigator():
     for episodes in (c['eps'], c['other'], c['eps']):
         traj = walk.run(episodes, navigator=nav)
         actions = [a.copy() for a in walk.actions]
-        assert _masks_match() > 0
+        assert N.masks_match() > 0
         early = walk.run(episodes, navigator=nav, check_every=1)
         assert early == traj
         assert len(walk.actions) == len(actions) and all(np.array_equal(x, y) for x, y in zip(walk.actions, actions))
@@ -162,14 +140,6 @@ def test_argmax_episode_runs_on_the_object_navigator():
         assert [tr['pred_objid'] for tr in traj] == [tr['pred_objid'] for tr in ref]
         found += sum(tr['pred_objid'] is not None for tr in traj)
     assert found >= 1
-
-
-class _FixedRng:
-    def __init__(self, u):
-        self.u = u
-
-    def random_sample(self, n):
-        return self.u
 
 
 def test_single_pass_sampled_episode_runs_on_the_object_navigator():
@@ -197,16 +167,9 @@ def test_single_pass_sampled_episode_runs_on_the_object_navigator():
         u = np.random.RandomState(100 + rnd).random_sample((T, B))
         traj, actions = sp.run(episodes, np.random.RandomState(100 + rnd), navigator=nav)
         torch.cuda.synchronize()
-        assert _masks_match() > 0
+        assert N.masks_match() > 0
         probs = [pr.float().cpu().numpy() for pr in sp.probs]
-        n = 0
-        for t in range(len(actions)):
-            want = rollout.SampledEpisode.sample(probs[t], _FixedRng(u[t]))
-            for b in range(B):
-                if nav.alive[t, b]:
-                    assert actions[t][b] == want[b], (t, b, actions[t][b], want[b])
-                    n += 1
-        assert n >= B
+        assert N.check_sampling(probs[:len(actions)], u, actions, nav.alive) >= B
         loss = float(sp.loss)
         grads = {id(p): (None if p.grad is None else p.grad.detach().clone()) for p in params}
         n_traj = sp.n_traj

@@ -57,132 +57,101 @@ __global__ __launch_bounds__(256) void nav_ndtw_kernel(Args a, Expert x) {
   ndtw_label(a, x, blockIdx.x, threadIdx.x, blockDim.x, DevSync(), row_s, ref_s);
 }
 
-int nav_sizes_bad(int B, int T, int W, int cap) {
-  return B < 1 || B > GOAT_NAV_MAX_B || T < 1 || T > GOAT_NAV_MAX_T || W < 1 || W > GOAT_NAV_MAX_W || cap < 1 || cap > GOAT_NAV_MAX_CAP;
+// objects: a REVERIE / SOON walk, whose O is a bucket of 1..GOAT_NAV_MAX_O object slots; an R2R walk has O = 0
+int nav_sizes_bad(int B, int T, int W, int O, int cap, bool objects) {
+  return B < 1 || B > GOAT_NAV_MAX_B || T < 1 || T > GOAT_NAV_MAX_T || W < 1 || W > GOAT_NAV_MAX_W || cap < 1 || cap > GOAT_NAV_MAX_CAP ||
+         (objects ? O < 1 || O > GOAT_NAV_MAX_O : O != 0);
 }
 
-}  // namespace
+// the walk's own fields first; a reset leaves everything behind `cap` zero, goat_nav_ndtw everything behind `step_tab`
+Args nav_args(const int64_t* scan_tab, int32_t* si, double* sd, int32_t* log, int B, int T, int W, int O, int cap, int t = 0,
+              int64_t ignoreid = 0, const int64_t* step_tab = nullptr, int32_t* ws = nullptr, const void* act = nullptr,
+              const double* u = nullptr, int mode = 0, int Gp = 0, int G = 0, int A = 0, const int64_t* obj_tab = nullptr,
+              const int64_t* ostep_tab = nullptr, const int32_t* goal = nullptr, int max_end = 0) {
+  return {scan_tab, step_tab, si, sd, log, ws, act, u, mode, t, B, T, Gp, G, W, A, cap, ignoreid, obj_tab, ostep_tab, goal, O, max_end};
+}
 
-extern "C" int goat_nav_state_ints(int T, int W, int cap) { return nav_sizes_bad(1, T, W, cap) ? 0 : Layout(cap, T, W).ints; }
-extern "C" int goat_nav_log_ints(int T, int cap) { return nav_sizes_bad(1, T, 1, cap) ? 0 : Layout(cap, T, 1).log_ints; }
+// a missing pointer (`rest`: those of the entry point beside the state) is GOAT_E_ARG, ahead of GOAT_E_SHAPE for the sizes
+int nav_check(const Args& a, bool objects, bool rest) {
+  if (!a.scan_tab || !a.si || !a.sd || !a.log || !rest) return GOAT_E_ARG;
+  return nav_sizes_bad(a.B, a.T, a.W, a.O, a.cap, objects) ? GOAT_E_SHAPE : 0;
+}
 
-extern "C" int goat_nav_reset(void* stream, const int64_t* scan_tab, int32_t* si, double* sd, int32_t* log, const int32_t* ep, int B,
-                              int T, int W, int cap) {
-  if (!scan_tab || !si || !sd || !log || !ep) return GOAT_E_ARG;
-  if (nav_sizes_bad(B, T, W, cap)) return GOAT_E_SHAPE;
-  Args a = {};
-  a.scan_tab = scan_tab;
-  a.si = si;
-  a.sd = sd;
-  a.log = log;
-  a.B = B;
-  a.T = T;
-  a.W = W;
-  a.cap = cap;
-  hipLaunchKernelGGL(nav_reset_kernel, dim3(B), dim3(256), 0, ST(stream), a, ep);
+int nav_reset(void* stream, const Args& a, const int32_t* ep, bool objects) {
+  if (const int bad = nav_check(a, objects, ep)) return bad;
+  hipLaunchKernelGGL(nav_reset_kernel, dim3(a.B), dim3(256), 0, ST(stream), a, ep);
   GOAT_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int goat_nav_step(void* stream, const int64_t* scan_tab, const int64_t* step_tab, int32_t* si, double* sd, int32_t* log,
-                             int32_t* ws, const void* act, const double* u, int mode, int t, int B, int T, int G_prev, int G, int W, int A,
-                             int cap, int64_t ignoreid) {
-  if (!scan_tab || !si || !sd || !log || !ws) return GOAT_E_ARG;
-  if (nav_sizes_bad(B, T, W, cap) || t < 0 || t > T) return GOAT_E_SHAPE;
-  if (mode != MODE_SAMPLE && mode != MODE_ARGMAX && mode != MODE_FORCED) return GOAT_E_ARG;
-  if (t < T && !step_tab) return GOAT_E_ARG;
-  if (t > 0 && (!act || (mode == MODE_SAMPLE && !u))) return GOAT_E_ARG;
-  if (t < T && (G < 2 || G > GOAT_NAV_MAX_G || G > cap + 2 || A < 4 || A % 4 != 0 || A > 64)) return GOAT_E_SHAPE;
-  if (t > 0 && (G_prev < 2 || G_prev > GOAT_NAV_MAX_G)) return GOAT_E_SHAPE;
-  Args a = {scan_tab, step_tab, si, sd, log, ws, act, u, mode, t, B, T, G_prev, G, W, A, cap, ignoreid};
-  const size_t lds = (size_t)(Layout(cap, T, W).small + HDR) * sizeof(int32_t);      // <= 11 KB at the limits
-  hipLaunchKernelGGL(nav_step_kernel, dim3(B), dim3(256), lds, ST(stream), a);
+// the step kernel and, where step t has tables (t < T), the batch-wide tail behind it
+int nav_step(void* stream, const Args& a, bool objects) {
+  const int t = a.t, T = a.T;
+  if (const int bad = nav_check(a, objects, a.ws && (!objects || (a.obj_tab && a.goal)))) return bad;
+  if ((objects && (a.max_end < 1 || a.max_end > GOAT_NAV_MAX_END)) || t < 0 || t > T) return GOAT_E_SHAPE;
+  if (a.mode != MODE_SAMPLE && a.mode != MODE_ARGMAX && a.mode != MODE_FORCED) return GOAT_E_ARG;
+  if (t < T && (!a.step_tab || (objects && !a.ostep_tab))) return GOAT_E_ARG;
+  if (t > 0 && (!a.act || (a.mode == MODE_SAMPLE && !a.u))) return GOAT_E_ARG;
+  if (t < T && (a.G < 2 || a.G > GOAT_NAV_MAX_G || a.G > a.cap + 2 || a.A < 4 || a.A % 4 != 0 || a.A > 64)) return GOAT_E_SHAPE;
+  if (t > 0 && (a.Gp < 2 || a.Gp > GOAT_NAV_MAX_G)) return GOAT_E_SHAPE;
+  // Layout::small + HDR ints: the R2R lists (<= 11 KB at the limits) and, with objects, the best-object record per node (<= 12 KB at
+  // cap = 254, W = 64)
+  const size_t lds = (size_t)(Layout(a.cap, T, a.W, a.O).small + HDR) * sizeof(int32_t);
+  hipLaunchKernelGGL(nav_step_kernel, dim3(a.B), dim3(256), lds, ST(stream), a);
   GOAT_LAUNCH_CHECK();
   if (t < T) {
     hipLaunchKernelGGL(nav_tail_kernel, dim3(1), dim3(256), 0, ST(stream), a);
     GOAT_LAUNCH_CHECK();
   }
   return 0;
+}
+
+}  // namespace
+
+extern "C" int goat_nav_state_ints(int T, int W, int cap) { return nav_sizes_bad(1, T, W, 0, cap, false) ? 0 : Layout(cap, T, W).ints; }
+extern "C" int goat_nav_log_ints(int T, int cap) { return nav_sizes_bad(1, T, 1, 0, cap, false) ? 0 : Layout(cap, T, 1).log_ints; }
+
+extern "C" int goat_nav_reset(void* stream, const int64_t* scan_tab, int32_t* si, double* sd, int32_t* log, const int32_t* ep, int B,
+                              int T, int W, int cap) {
+  return nav_reset(stream, nav_args(scan_tab, si, sd, log, B, T, W, 0, cap), ep, false);
+}
+
+extern "C" int goat_nav_step(void* stream, const int64_t* scan_tab, const int64_t* step_tab, int32_t* si, double* sd, int32_t* log,
+                             int32_t* ws, const void* act, const double* u, int mode, int t, int B, int T, int G_prev, int G, int W, int A,
+                             int cap, int64_t ignoreid) {
+  return nav_step(stream, nav_args(scan_tab, si, sd, log, B, T, W, 0, cap, t, ignoreid, step_tab, ws, act, u, mode, G_prev, G, A), false);
 }
 
 // goat_nav_obj_*: the same two kernels over a REVERIE / SOON walk.  Args::O > 0 turns on the places where EpisodePlanner.build_step
 // branches on its objects: the panorama is W views + O object slots wide, the pool stride of the node embeddings follows it, the
 // object tables of the step are written beside the 21 others, [MEM] stays selectable, and an argmax walk records the best object
 // of every scored node.  One object slot per thread for loc_fts; the tail forms the object CSRs from the same prefix sums.
-namespace {
-
-int nav_obj_sizes_bad(int B, int T, int W, int O, int cap) {
-  return nav_sizes_bad(B, T, W, cap) || O < 1 || O > GOAT_NAV_MAX_O;
-}
-
-}  // namespace
-
 extern "C" int goat_nav_obj_state_ints(int T, int W, int O, int cap) {
-  return nav_obj_sizes_bad(1, T, W, O, cap) ? 0 : Layout(cap, T, W, O).ints;
+  return nav_sizes_bad(1, T, W, O, cap, true) ? 0 : Layout(cap, T, W, O).ints;
 }
 
 extern "C" int goat_nav_obj_reset(void* stream, const int64_t* scan_tab, int32_t* si, double* sd, int32_t* log, const int32_t* ep, int B,
                                   int T, int W, int O, int cap) {
-  if (!scan_tab || !si || !sd || !log || !ep) return GOAT_E_ARG;
-  if (nav_obj_sizes_bad(B, T, W, O, cap)) return GOAT_E_SHAPE;
-  Args a = {};
-  a.scan_tab = scan_tab;
-  a.si = si;
-  a.sd = sd;
-  a.log = log;
-  a.B = B;
-  a.T = T;
-  a.W = W;
-  a.cap = cap;
-  a.O = O;
-  hipLaunchKernelGGL(nav_reset_kernel, dim3(B), dim3(256), 0, ST(stream), a, ep);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return nav_reset(stream, nav_args(scan_tab, si, sd, log, B, T, W, O, cap), ep, true);
 }
 
 extern "C" int goat_nav_obj_step(void* stream, const int64_t* scan_tab, const int64_t* obj_tab, const int64_t* step_tab,
                                  const int64_t* ostep_tab, int32_t* si, double* sd, int32_t* log, int32_t* ws, const void* act,
                                  const double* u, const int32_t* goal, int mode, int t, int B, int T, int G_prev, int G, int W, int O,
                                  int max_end, int A, int cap, int64_t ignoreid) {
-  if (!scan_tab || !obj_tab || !si || !sd || !log || !ws || !goal) return GOAT_E_ARG;
-  if (nav_obj_sizes_bad(B, T, W, O, cap) || max_end < 1 || max_end > GOAT_NAV_MAX_END || t < 0 || t > T) return GOAT_E_SHAPE;
-  if (mode != MODE_SAMPLE && mode != MODE_ARGMAX && mode != MODE_FORCED) return GOAT_E_ARG;
-  if (t < T && (!step_tab || !ostep_tab)) return GOAT_E_ARG;
-  if (t > 0 && (!act || (mode == MODE_SAMPLE && !u))) return GOAT_E_ARG;
-  if (t < T && (G < 2 || G > GOAT_NAV_MAX_G || G > cap + 2 || A < 4 || A % 4 != 0 || A > 64)) return GOAT_E_SHAPE;
-  if (t > 0 && (G_prev < 2 || G_prev > GOAT_NAV_MAX_G)) return GOAT_E_SHAPE;
-  Args a = {scan_tab, step_tab, si, sd, log, ws, act, u, mode, t, B, T, G_prev, G, W, A, cap, ignoreid, obj_tab, ostep_tab, goal, O, max_end};
-  // Layout::small + HDR ints: the R2R lists and the best-object record per node, <= 12 KB at the limits (cap = 254, W = 64)
-  const size_t lds = (size_t)(Layout(cap, T, W, O).small + HDR) * sizeof(int32_t);
-  hipLaunchKernelGGL(nav_step_kernel, dim3(B), dim3(256), lds, ST(stream), a);
-  GOAT_LAUNCH_CHECK();
-  if (t < T) {
-    hipLaunchKernelGGL(nav_tail_kernel, dim3(1), dim3(256), 0, ST(stream), a);
-    GOAT_LAUNCH_CHECK();
-  }
-  return 0;
+  return nav_step(stream, nav_args(scan_tab, si, sd, log, B, T, W, O, cap, t, ignoreid, step_tab, ws, act, u, mode, G_prev, G, A, obj_tab,
+                                   ostep_tab, goal, max_end), true);
 }
 
 extern "C" int goat_nav_expert_doubles(int cap, int max_ref) {
-  return (nav_sizes_bad(1, 1, 1, cap) || max_ref < 1 || max_ref > GOAT_NAV_MAX_REF) ? 0 : expert_doubles(cap, max_ref);
+  return (nav_sizes_bad(1, 1, 1, 0, cap, false) || max_ref < 1 || max_ref > GOAT_NAV_MAX_REF) ? 0 : expert_doubles(cap, max_ref);
 }
 
 extern "C" int goat_nav_ndtw(void* stream, const int64_t* scan_tab, const int64_t* step_tab, int32_t* si, double* sd, int32_t* log,
                              const int32_t* ref, double* xd, int t, int B, int T, int W, int cap, int max_ref, int64_t ignoreid) {
-  if (!scan_tab || !step_tab || !si || !sd || !log || !ref || !xd) return GOAT_E_ARG;
-  if (nav_sizes_bad(B, T, W, cap) || max_ref < 1 || max_ref > GOAT_NAV_MAX_REF || t < 0 || t >= T) return GOAT_E_SHAPE;
-  Args a = {};
-  a.scan_tab = scan_tab;
-  a.step_tab = step_tab;
-  a.si = si;
-  a.sd = sd;
-  a.log = log;
-  a.t = t;
-  a.B = B;
-  a.T = T;
-  a.W = W;
-  a.cap = cap;
-  a.ignoreid = ignoreid;
+  const Args a = nav_args(scan_tab, si, sd, log, B, T, W, 0, cap, t, ignoreid, step_tab);
+  if (const int bad = nav_check(a, false, step_tab && ref && xd)) return bad;
+  if (max_ref < 1 || max_ref > GOAT_NAV_MAX_REF || t < 0 || t >= T) return GOAT_E_SHAPE;
   const Expert x = {ref, xd, max_ref};
   hipLaunchKernelGGL(nav_ndtw_kernel, dim3(B), dim3(256), 0, ST(stream), a, x);
   GOAT_LAUNCH_CHECK();

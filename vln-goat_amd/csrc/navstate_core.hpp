@@ -36,7 +36,7 @@ enum { OB_START = 0, OB_ROW, OB_DIR, OB_BOX, OB_NAME, OB_COUNT };
 enum { OT_OBJ_IDX = 0, OT_OBJ_START, OT_OBJ_LENS, OT_OBJ_NAMES, OT_VP_OBJ, OT_OBJ_TARGET, OT_OCAT_IDX, OT_OCAT_START, OT_OCAT_INV_IDX,
        OT_OCAT_INV_START, OT_COUNT };
 
-struct Layout {      // ints of an episode's private state / of its read-back block; navdev.py computes the same numbers
+struct Layout {      // ints of an episode's private state / of its read-back block; navdev.py asks goat_nav_*_ints for the sizes
   int cap, T, W, acc;
   int o_vp, o_vis, o_step, o_kind, o_nacc, o_ord, o_slot, o_scored, o_iscand, o_acc, o_P, o_rows, o_cnode, o_seg, o_best, o_stk, small, ints;
   int l_hs, l_hops, log_ints;
@@ -54,6 +54,20 @@ struct Layout {      // ints of an episode's private state / of its read-back bl
     o_stk = o; o += 2 * cap + 2;
     ints = o;
     l_hs = HDR;  l_hops = l_hs + T + 2;  log_ints = l_hops + (T + 1) * cap;
+  }
+};
+
+// ints of the workspace `ws` of the batch-wide tail (navdev.workspace computes the same numbers): [B + 1] bases of the view rows and of
+// the node-embedding tokens, one owner per pool row of the last step, the live count and, with objects, [B + 1] object bases behind it
+struct Workspace {
+  int fbase, cbase, owner, live_at, obase, ints;
+  NAV_HD Workspace(int B, int T, int W, int O = 0) {
+    fbase = 0;
+    cbase = B + 1;
+    owner = 2 * (B + 1);
+    live_at = owner + T * (B * (W + O) + B) + B;
+    obase = live_at + 1;
+    ints = obase + (O > 0 ? B + 1 : 0);
   }
 };
 
@@ -223,53 +237,72 @@ NAV_HD inline double toward_zero(double c) {        // numpy.nextafter(c, 0.0)
   return c;
 }
 
+// The action of step tp in the mode of the walk; an episode that has ended stops.  Thread 0.
+NAV_HD inline int mode_action(const Args& a, int b, int tp, int ended) {
+#pragma clang fp contract(off)
+  if (a.mode == MODE_SAMPLE) {           // SampledEpisode.sample (sampled.py:115-121): float64 cumulative sum in slot order
+    const float* p = reinterpret_cast<const float*>(a.act) + (int64_t)b * a.Gp;
+    double total = 0.0;
+    for (int g = 0; g < a.Gp; ++g) total = total + (double)p[g];
+    const double lim = toward_zero(total);
+    double x = a.u[(int64_t)tp * a.B + b] * total;
+    if (lim < x) x = lim;
+    double c = 0.0;
+    int act = a.Gp;
+    for (int g = 0; g < a.Gp; ++g) {
+      c = c + (double)p[g];
+      if (c > x) {
+        act = g;
+        break;
+      }
+    }
+    return ended ? 0 : act;
+  }
+  if (a.mode == MODE_ARGMAX) return ended ? 0 : (int)reinterpret_cast<const float*>(a.act)[b];
+  return reinterpret_cast<const int32_t*>(a.act)[(int64_t)tp * a.B + b];
+}
+
+// node_stop_scores[viewpoint] = {'stop': score} of an argmax walk for the viewpoint `cur` the live episode stands on.  Thread 0.
+NAV_HD inline void record_stop_score(const Args& a, const Ep& e, int b, int cur) {
+  const float* back = reinterpret_cast<const float*>(a.act);
+  const int ci = e.find(cur);
+  if (ci < 0) return;
+  bool seen = false;
+  for (int i = 0; i < e.H[H_NSCORED]; ++i) seen = seen || e.S[e.L.o_scored + i] == ci;
+  if (!seen) e.S[e.L.o_scored + e.H[H_NSCORED]++] = ci;
+  e.score[ci] = (double)back[a.B + b];
+  // ['og'] = obj_ids[best object] | None: row 2 is read only where the viewpoint has objects (elsewhere it holds the argmax
+  // of an all -inf row less v + 2, a negative number)
+  if (a.O > 0) e.S[e.L.o_best + ci] = e.H[H_OLEN] > 0 ? (int)back[2 * a.B + b] : -1;
+}
+
+// FloydGraph.path from node `from` (-1: the viewpoint is not in the map) to node `to`, its viewpoints logged behind the `hopn` hops the
+// walk has made -> hops; 0 with the status word set where there is no path or the hop log has no room for it.  Thread 0.
+NAV_HD inline int log_path(const Args& a, const Ep& e, int tp, int from, int to, int hopn) {
+  const int cap = a.cap, room = (a.T + 1) * cap - hopn;
+  int wrote = 0;
+  int32_t* out = e.hops + hopn;
+  const int32_t* vp = e.S + e.L.o_vp;
+  const int n = from < 0 ? -1 : expand_path(e.Sb + e.L.o_P, cap, from, to, e.Sb + e.L.o_stk, 2 * cap + 2, [&](int node) {
+    if (wrote < room) out[wrote] = vp[node];
+    ++wrote;
+  });
+  if (n >= 1 && wrote <= room) return n;
+  e.fail(ST_PATH, tp);
+  return 0;
+}
+
 // EpisodePlanner.advance of step tp (episodes.py:300-357) with the action of the mode.  Collective.
 template <class Sync>
 NAV_HD inline void advance_episode(const Args& a, const Ep& e, int b, int tp, int tid, int nt, Sync sync) {
 #pragma clang fp contract(off)
-  const int cap = a.cap;
   const int ended = e.H[H_ENDED];
   sync();
   if (tid == 0) {
-    const int32_t* P = e.Sb + e.L.o_P;
     const int cur = e.H[H_CUR];
     const bool argmax = a.mode == MODE_ARGMAX;
-    int act = 0;
-    if (a.mode == MODE_SAMPLE) {           // SampledEpisode.sample (sampled.py:115-121): float64 cumulative sum in slot order
-      const float* p = reinterpret_cast<const float*>(a.act) + (int64_t)b * a.Gp;
-      double total = 0.0;
-      for (int g = 0; g < a.Gp; ++g) total = total + (double)p[g];
-      const double lim = toward_zero(total);
-      double x = a.u[(int64_t)tp * a.B + b] * total;
-      if (lim < x) x = lim;
-      double c = 0.0;
-      act = a.Gp;
-      for (int g = 0; g < a.Gp; ++g) {
-        c = c + (double)p[g];
-        if (c > x) {
-          act = g;
-          break;
-        }
-      }
-      if (ended) act = 0;
-    } else if (argmax) {
-      const float* back = reinterpret_cast<const float*>(a.act);
-      act = ended ? 0 : (int)back[b];
-      if (!ended) {                         // node_stop_scores[viewpoint] = {'stop': score}
-        const int ci = e.find(cur);
-        if (ci >= 0) {
-          bool seen = false;
-          for (int i = 0; i < e.H[H_NSCORED]; ++i) seen = seen || e.S[e.L.o_scored + i] == ci;
-          if (!seen) e.S[e.L.o_scored + e.H[H_NSCORED]++] = ci;
-          e.score[ci] = (double)back[a.B + b];
-          // ['og'] = obj_ids[best object] | None: row 2 is read only where the viewpoint has objects (elsewhere it holds the argmax
-          // of an all -inf row less v + 2, a negative number)
-          if (a.O > 0) e.S[e.L.o_best + ci] = e.H[H_OLEN] > 0 ? (int)back[2 * a.B + b] : -1;
-        }
-      }
-    } else {
-      act = reinterpret_cast<const int32_t*>(a.act)[(int64_t)tp * a.B + b];
-    }
+    const int act = mode_action(a, b, tp, ended);
+    if (argmax && !ended) record_stop_score(a, e, b, cur);
     a.log[(int64_t)tp * a.B + b] = act;
     a.log[(int64_t)(a.T + tp) * a.B + b] = !ended;
     const bool stop = argmax ? act == 0 : cur == e.H[H_GOAL];
@@ -282,20 +315,11 @@ NAV_HD inline void advance_episode(const Args& a, const Ep& e, int b, int tp, in
       if (act < 0 || act >= nslots || act == 1 || (act > 1 && e.S[e.L.o_vis + e.S[e.L.o_ord + act - 2]])) {
         e.fail(ST_ACTION, tp);                 // the host planner raises here; the walk goes on as if the episode had stopped
       } else if (act >= 2) {
-        const int ci = e.find(cur), dn = e.S[e.L.o_ord + act - 2];
-        const int room = (a.T + 1) * cap - hopn;
-        int wrote = 0;
-        int32_t* out = e.hops + hopn;
-        const int32_t* vp = e.S + e.L.o_vp;
-        const int n = ci < 0 ? -1 : expand_path(P, cap, ci, dn, e.Sb + e.L.o_stk, 2 * cap + 2, [&](int node) {
-          if (wrote < room) out[wrote] = vp[node];
-          ++wrote;
-        });
-        if (n < 1 || wrote > room) {
-          e.fail(ST_PATH, tp);
-        } else {
-          dest = vp[dn];
-          const int prev = n == 1 ? cur : out[n - 2];
+        const int dn = e.S[e.L.o_ord + act - 2];
+        const int n = log_path(a, e, tp, e.find(cur), dn, hopn);
+        if (n > 0) {
+          dest = e.S[e.L.o_vp + dn];
+          const int prev = n == 1 ? cur : e.hops[hopn + n - 2];
           const int32_t* cs = scan_ptr<int32_t>(a, SC_CAND_START);
           const int32_t* nb = scan_ptr<int32_t>(a, SC_CAND_NB);
           const int32_t* pt = scan_ptr<int32_t>(a, SC_CAND_POINT);
@@ -323,17 +347,8 @@ NAV_HD inline void advance_episode(const Args& a, const Ep& e, int b, int tp, in
       }
       const int ci = e.find(cur);
       if (ci >= 0 && best != ci) {
-        const int room = (a.T + 1) * cap - hopn;
-        int wrote = 0;
-        int32_t* out = e.hops + hopn;
-        const int32_t* vp = e.S + e.L.o_vp;
-        const int n = expand_path(P, cap, ci, best, e.Sb + e.L.o_stk, 2 * cap + 2, [&](int node) {
-          if (wrote < room) out[wrote] = vp[node];
-          ++wrote;
-        });
-        if (n < 1 || wrote > room) {
-          e.fail(ST_PATH, tp);
-        } else {
+        const int n = log_path(a, e, tp, ci, best, hopn);
+        if (n > 0) {
           e.H[H_BT_START] = hopn;
           e.H[H_BT_N] = n;
           hopn += n;
@@ -360,295 +375,344 @@ NAV_HD inline void angle_row(float* out, int A, double h, double el) {        //
   for (int x = 0; x < A; ++x) out[x] = f[x % 4];
 }
 
+// The serial jobs of EpisodePlanner.build_step of step a.t (episodes.py:245-298) for one episode, in its order.  Thread 0.
+
+// panorama_inputs: the candidates' views, then the views no candidate used; with objects, the viewpoint's count clamped to the bucket
+NAV_HD inline void pano_order(const Args& a, const Ep& e, int b) {
+  const int W = a.W, O = a.O, t = a.t, cur = e.H[H_CUR];
+  const Layout& L = e.L;
+  int32_t* S = e.S;
+  const int32_t* cs = scan_ptr<int32_t>(a, SC_CAND_START);
+  const int32_t* pt = scan_ptr<int32_t>(a, SC_CAND_POINT);
+  const int c0 = cs[cur];
+  const int fr = scan_ptr<int32_t>(a, SC_FEATURE_ROW)[cur];
+  const int ncand = cs[cur + 1] - c0;
+  uint64_t used = 0;
+  int len = 0;
+  for (int c = 0; c < ncand; ++c) {
+    if (len < W) S[L.o_rows + len] = fr * 36 + pt[c0 + c];
+    used |= (uint64_t)1 << pt[c0 + c];
+    ++len;
+  }
+  for (int k = 0; k < 36; ++k)
+    if (!((used >> k) & 1)) {
+      if (len < W) S[L.o_rows + len] = fr * 36 + k;
+      ++len;
+    }
+  if (len > W) {
+    e.fail(ST_PANO, t);
+    len = W;
+  }
+  e.H[H_VLEN] = len;
+  e.H[H_NCAND] = ncand < W ? ncand : W;
+  step_ptr<int64_t>(a, TB_VIEW_LENS)[b] = len;
+  if (O > 0) {      // the objects of the viewpoint: contiguous rows of ObjectStore.table
+    const int32_t* os = obj_ptr<int32_t>(a, OB_START);
+    int olen = os[cur + 1] - os[cur];
+    if (olen > O) {
+      e.fail(ST_OBJ, t);
+      olen = O;
+    }
+    e.H[H_OLEN] = olen;
+    ostep_ptr<int64_t>(a, OT_OBJ_LENS)[b] = olen;
+  }
+}
+
+// note_step (nav_inputs.py:233-243)
+NAV_HD inline void note_step(const Args& a, const Ep& e, int b) {
+  const int t = a.t, B = a.B, WT = a.W + a.O, ended = e.H[H_ENDED], cur = e.H[H_CUR], n = e.H[H_N];
+  const int view_base = t * (B * WT + B), fused_base = view_base + B * WT;      // store.advance(B, te.WT)
+  const Layout& L = e.L;
+  int32_t* S = e.S;
+  const int32_t* nb = scan_ptr<int32_t>(a, SC_CAND_NB);
+  const int c0 = scan_ptr<int32_t>(a, SC_CAND_START)[cur];
+  for (int i = 0; i < n; ++i) S[L.o_iscand + i] = 0;
+  const int ci = e.find(cur);
+  if (!ended && ci >= 0) {
+    S[L.o_step + ci] = t + 1;
+    S[L.o_kind + ci] = KIND_SET;
+    S[L.o_nacc + ci] = 1;
+    e.Sb[L.o_acc + ci * L.acc] = fused_base + b;
+  }
+  for (int c = 0; c < e.H[H_NCAND]; ++c) {
+    const int j = e.find(nb[c0 + c]);
+    S[L.o_cnode + c] = j;
+    if (j < 0) continue;
+    S[L.o_iscand + j] = 1;
+    if (!ended && !S[L.o_vis + j]) {            // NodeEmbedStore.accumulate
+      const int row = view_base + b * WT + c;
+      int32_t* acc = e.Sb + L.o_acc + j * L.acc;
+      if (S[L.o_kind + j] == KIND_NONE) {
+        S[L.o_kind + j] = KIND_ACC;
+        S[L.o_nacc + j] = 1;
+        acc[0] = row;
+      } else if (S[L.o_nacc + j] < L.acc) {
+        S[L.o_kind + j] = KIND_ACC;
+        acc[S[L.o_nacc + j]++] = row;
+      } else {
+        e.fail(ST_PATH, t);
+      }
+    }
+  }
+}
+
+// gmap_order: [stop], [MEM], the visited nodes, the unvisited ones, each in insertion order; behind note_step, the episode's share of the
+// node-embedding CSR
+NAV_HD inline void map_order(const Args& a, const Ep& e) {
+  const int t = a.t, G = a.G, n = e.H[H_N];
+  const Layout& L = e.L;
+  int32_t* S = e.S;
+  int nv = 0;
+  for (int i = 0; i < n; ++i)
+    if (S[L.o_vis + i]) S[L.o_ord + nv++] = i;
+  int nu = nv;
+  for (int i = 0; i < n; ++i)
+    if (!S[L.o_vis + i]) S[L.o_ord + nu++] = i;
+  for (int k = 0; k < n; ++k) S[L.o_slot + S[L.o_ord + k]] = k + 2;
+  e.H[H_NOLEFT] = nu == nv;
+  int nslots = n + 2;
+  if (nslots > G) {
+    e.fail(ST_MAP, t);
+    nslots = G;
+  }
+  e.H[H_NSLOT] = nslots;
+  // the episode's share of the node-embedding CSR (NodeEmbedStore.csr): tokens per slot as a running sum
+  int tok = 0;
+  S[L.o_seg] = 0;
+  for (int g = 0; g < G; ++g) {
+    int cnt = 0;
+    if (g == 1 && t > 0) cnt = 1;
+    else if (g >= 2 && g < nslots) cnt = S[L.o_nacc + S[L.o_ord + g - 2]];
+    tok += cnt;
+    S[L.o_seg + g + 1] = tok;
+  }
+}
+
+// the two DAgger labels of the step: the node to move to and, with objects, the object to pick
+NAV_HD inline void teacher_labels(const Args& a, const Ep& e, int b) {
+#pragma clang fp contract(off)
+  const int ended = e.H[H_ENDED], cur = e.H[H_CUR], nslots = e.H[H_NSLOT];
+  const Layout& L = e.L;
+  const int32_t* S = e.S;
+  // teacher_action(imitation_learning=False) (nav_inputs.py:205-218): strict <, the first minimum wins
+  int64_t target = a.ignoreid;
+  if (!ended) {
+    const int goal = e.H[H_GOAL];
+    if (cur == goal) {
+      target = 0;
+    } else {
+      const int s = e.H[H_SCAN];
+      const int off = scan_ptr<int32_t>(a, SC_SCAN_OFF)[s], ns = scan_ptr<int32_t>(a, SC_SCAN_N)[s];
+      const double* dist = scan_ptr<double>(a, SC_DIST) + scan_ptr<int64_t>(a, SC_DIST_OFF)[s];
+      double best = INFINITY;
+      for (int g = 2; g < nslots; ++g) {
+        const int node = S[L.o_ord + g - 2];
+        if (S[L.o_vis + node]) continue;
+        const int k = S[L.o_vp + node] - off;
+        const double d = dist[(int64_t)k * ns + (goal - off)] + dist[(int64_t)(cur - off) * ns + k];
+        if (d < best) {
+          best = d;
+          target = g;
+        }
+      }
+    }
+  }
+  step_ptr<int64_t>(a, TB_TARGET)[b] = target;
+  if (a.O > 0) {
+    // teacher_object (nav_inputs.py:175-186): on one of the episode's end viewpoints the slot of the target object among [stop],
+    // [MEM], the views and the objects; the ignore value elsewhere and where the target is not among the viewpoint's objects
+    const int olen = e.H[H_OLEN], len = e.H[H_VLEN];
+    int64_t ot = a.ignoreid;
+    if (!ended) {
+      const int32_t* goal = a.goal + (int64_t)b * a.max_end * 2;
+      for (int k = 0; k < a.max_end; ++k)
+        if (goal[2 * k] == cur) {         // (a viewpoint listed twice carries the same index)
+          const int j = goal[2 * k + 1];
+          if (j >= 0 && j < olen) ot = j + len + 2;
+          break;
+        }
+    }
+    ostep_ptr<int64_t>(a, OT_OBJ_TARGET)[b] = ot;
+  }
+}
+
+// The token tables of the step, spread over the threads.  bh, be: heading and elevation of the view the episode looks along.
+
+// panorama tokens (panorama_inputs / panorama_object_inputs, vp_inputs' masks)
+NAV_HD inline void pano_tokens(const Args& a, const Ep& e, int b, double bh, double be, int tid, int nt) {
+#pragma clang fp contract(off)
+  const int W = a.W, A = a.A, C = a.A + 3;
+  const int O = a.O, WT = W + O;        // object walks: O object slots behind the W views of every panorama (panorama_object_inputs)
+  const Layout& L = e.L;
+  const int32_t* S = e.S;
+  const int cur = e.H[H_CUR], view = e.H[H_VIEW], vlen = e.H[H_VLEN], ncand = e.H[H_NCAND];
+  const int c0 = scan_ptr<int32_t>(a, SC_CAND_START)[cur];
+  const double* cang = scan_ptr<double>(a, SC_CAND_ANG);
+  const float* vaf = scan_ptr<float>(a, SC_VAF);
+  const int fr36 = scan_ptr<int32_t>(a, SC_FEATURE_ROW)[cur] * 36;
+  float* loc = step_ptr<float>(a, TB_LOC_FTS) + (int64_t)b * WT * C;
+  int64_t* ty = step_ptr<int64_t>(a, TB_NAV_TYPES) + (int64_t)b * WT;
+  uint8_t* vm = step_ptr<uint8_t>(a, TB_VP_MASK) + (int64_t)b * (WT + 2);
+  uint8_t* vn = step_ptr<uint8_t>(a, TB_VP_NAV) + (int64_t)b * (WT + 2);
+  const int olen = O > 0 ? e.H[H_OLEN] : 0;
+  const int o0 = O > 0 ? obj_ptr<int32_t>(a, OB_START)[cur] : 0;
+  for (int j = tid; j < WT; j += nt) {
+    float* row = loc + j * C;
+    if (j >= vlen && j < vlen + olen) {
+      // ObjectStore.attributes: the object tokens follow the views (nav type 2): [angle_feature(direction - base) | box]
+      const double* dir = obj_ptr<double>(a, OB_DIR) + (int64_t)(o0 + j - vlen) * 2;
+      const float* box = obj_ptr<float>(a, OB_BOX) + (int64_t)(o0 + j - vlen) * 3;
+      angle_row(row, A, dir[0] - bh, dir[1] - be);
+      for (int x = 0; x < 3; ++x) row[A + x] = box[x];
+      ty[j] = 2;
+      continue;
+    }
+    if (j < ncand) {
+      angle_row(row, A, cang[(c0 + j) * 2] - bh, cang[(c0 + j) * 2 + 1] - be);
+    } else if (j < vlen) {
+      const float* src = vaf + ((int64_t)view * 36 + (S[L.o_rows + j] - fr36)) * A;
+      for (int x = 0; x < A; ++x) row[x] = src[x];
+    } else {
+      for (int x = 0; x < A; ++x) row[x] = 0.0f;
+    }
+    for (int x = A; x < C; ++x) row[x] = j < vlen ? 1.0f : 0.0f;
+    ty[j] = j < ncand ? 1 : 0;
+  }
+  for (int j = tid; j < WT + 2; j += nt) {
+    vm[j] = j < vlen + olen + 2;
+    vn[j] = j == 0 ? 1 : (j == 1 ? 0 : (j - 2 < ncand));
+  }
+  if (O > 0) {
+    uint8_t* vo = ostep_ptr<uint8_t>(a, OT_VP_OBJ) + (int64_t)b * (WT + 2);
+    int64_t* names = ostep_ptr<int64_t>(a, OT_OBJ_NAMES) + (int64_t)b * O;
+    const int64_t* name = obj_ptr<int64_t>(a, OB_NAME);
+    // vp_inputs: the head of vp_nav_masks ([stop] true, [MEM] false), then nav_types == 2
+    for (int j = tid; j < WT + 2; j += nt) vo[j] = j == 0 ? 1 : (j - 2 >= vlen && j - 2 < vlen + olen);
+    for (int j = tid; j < O; j += nt) names[j] = j < olen ? name[o0 + j] : 0;
+  }
+}
+
+// map tokens (gmap_inputs, GraphMap.get_pos_fts / pair_dists) and the logit fusion matrix
+NAV_HD inline void map_tokens(const Args& a, const Ep& e, int b, double bh, double be, int tid, int nt) {
+#pragma clang fp contract(off)
+  const int cap = a.cap, G = a.G, A = a.A, C = a.A + 3, O = a.O, WT = a.W + a.O;
+  const Layout& L = e.L;
+  const int32_t* S = e.S;
+  const int cur = e.H[H_CUR], ncand = e.H[H_NCAND], nslots = e.H[H_NSLOT];
+  const double* pos = scan_ptr<double>(a, SC_POS);
+  const int32_t* P = e.Sb + L.o_P;
+  int64_t* sid = step_ptr<int64_t>(a, TB_STEP_IDS) + (int64_t)b * G;
+  uint8_t* vmask = step_ptr<uint8_t>(a, TB_VISITED) + (int64_t)b * G;
+  uint8_t* gmask = step_ptr<uint8_t>(a, TB_GMASK) + (int64_t)b * G;
+  float* scale = step_ptr<float>(a, TB_CSR_SCALE) + (int64_t)b * G;
+  float* gp = step_ptr<float>(a, TB_GMAP_POS) + (int64_t)b * G * C;
+  const int ci = e.find(cur);
+  const double ax = pos[cur * 3], ay = pos[cur * 3 + 1], az = pos[cur * 3 + 2];
+  for (int g = tid; g < G; g += nt) {
+    float* row = gp + g * C;
+    const bool real = g >= 2 && g < nslots;
+    const int node = real ? S[L.o_ord + g - 2] : -1;
+    sid[g] = real ? S[L.o_step + node] : 0;
+    vmask[g] = g == 1 ? 1 : (real ? S[L.o_vis + node] != 0 : 0);
+    gmask[g] = g < nslots && (g != 1 || O > 0);      // (gmap_inputs(mem_selectable=has_obj): the REVERIE builder keeps [MEM])
+    scale[g] = (real && S[L.o_kind + node] == KIND_ACC) ? (float)(1.0 / (double)S[L.o_nacc + node]) : 1.0f;
+    if (g >= nslots) {
+      for (int x = 0; x < C; ++x) row[x] = 0.0f;
+      continue;
+    }
+    float h32 = 0.0f, e32 = 0.0f;
+    double line = 0.0, md = 0.0, hops = 0.0;
+    if (real) {
+      const int v = S[L.o_vp + node];
+      const double by = pos[v * 3 + 1];
+      const double dx = pos[v * 3] - ax, dy = by - ay, dz = pos[v * 3 + 2] - az;       // navsim.rel_pos
+      const double xy = fmax(sqrt(dx * dx + dy * dy), 1e-8);
+      const double xyz = fmax(sqrt(dx * dx + dy * dy + dz * dz), 1e-8);
+      double hd = asin(dx / xy);
+      if (by < ay) hd = 3.141592653589793 - hd;
+      const double el = asin(dz / xyz);
+      h32 = (float)(hd - bh);
+      e32 = (float)(el - be);
+      line = xyz / 30.0;
+      if (ci >= 0 && node != ci) {
+        md = e.D[ci * cap + node] / 30.0;
+        int32_t stk[256];
+        const int nh = expand_path(P, cap, ci, node, stk, 256, [](int) {});
+        hops = (double)(nh < 0 ? 0 : nh) / 10.0;
+      }
+    }
+    // get_angle_fts: sin / cos of the float32 angles
+    const float f[4] = {(float)sin((double)h32), (float)cos((double)h32), (float)sin((double)e32), (float)cos((double)e32)};
+    for (int x = 0; x < A; ++x) row[x] = f[x % 4];
+    row[A] = (float)line;
+    row[A + 1] = (float)md;
+    row[A + 2] = (float)hops;
+  }
+  float* pair = step_ptr<float>(a, TB_PAIR) + (int64_t)b * G * G;
+  for (int x = tid; x < G * G; x += nt) {
+    const int g = x / G, h = x % G;
+    float v = 0.0f;
+    if (g >= 2 && h >= 2 && g < nslots && h < nslots && g != h) v = (float)e.D[S[L.o_ord + g - 2] * cap + S[L.o_ord + h - 2]];
+    pair[x] = v;
+  }
+  // nav_fusion_matrix (nav_model.py:231-253)
+  float* fus = step_ptr<float>(a, TB_FUSION) + (int64_t)b * G * (WT + 2);
+  for (int x = tid; x < G * (WT + 2); x += nt) {
+    const int g = x / (WT + 2), j = x % (WT + 2);
+    float v = 0.0f;
+    if (g >= 2 && g < nslots && j >= 2 && j - 2 < ncand) {
+      const int node = S[L.o_ord + g - 2], cn = S[L.o_cnode + j - 2];
+      if (!S[L.o_vis + node] && cn >= 0) {
+        if (cn == node) v = 1.0f;
+        else if (S[L.o_vis + cn] && !S[L.o_iscand + node]) v = 1.0f;
+      }
+    }
+    fus[x] = v;
+  }
+}
+
+// vp_inputs: the start node's row in every slot, the candidates' rows behind it (rows of gmap_pos_fts, all of them written)
+NAV_HD inline void vp_tokens(const Args& a, const Ep& e, int b, int tid, int nt) {
+  const int G = a.G, C = a.A + 3, WT = a.W + a.O;
+  const Layout& L = e.L;
+  const int32_t* S = e.S;
+  const int ncand = e.H[H_NCAND], nslots = e.H[H_NSLOT];
+  const float* gp = step_ptr<float>(a, TB_GMAP_POS) + (int64_t)b * G * C;
+  float* vp = step_ptr<float>(a, TB_VP_POS) + (int64_t)b * (WT + 2) * 2 * C;
+  const int sn = e.find(e.H[H_START]);
+  const int sslot = sn >= 0 ? S[L.o_slot + sn] : G;
+  for (int x = tid; x < (WT + 2) * 2 * C; x += nt) {
+    const int j = x / (2 * C), c = x % (2 * C);
+    float v = 0.0f;
+    if (c < C) {
+      if (sslot < nslots) v = gp[sslot * C + c];
+    } else if (j >= 2 && j - 2 < ncand) {
+      const int cn = S[L.o_cnode + j - 2];
+      const int slot = cn >= 0 ? S[L.o_slot + cn] : G;
+      if (slot < nslots) v = gp[slot * C + c - C];
+    }
+    vp[x] = v;
+  }
+}
+
 // EpisodePlanner.build_step of step t (episodes.py:245-298) for one episode: every table row of the episode except the batch-wide
 // compact CSRs, whose pieces it leaves in the state for nav_tail.  Collective.
 template <class Sync>
 NAV_HD inline void build_episode(const Args& a, const Ep& e, int b, int tid, int nt, Sync sync) {
-#pragma clang fp contract(off)
-  const int cap = a.cap, t = a.t, B = a.B, G = a.G, W = a.W, A = a.A, C = a.A + 3;
-  const int O = a.O, WT = W + O;        // object walks: O object slots behind the W views of every panorama (panorama_object_inputs)
-  const Layout& L = e.L;
-  int32_t* S = e.S;
-  const int32_t* cs = scan_ptr<int32_t>(a, SC_CAND_START);
-  const int32_t* nb = scan_ptr<int32_t>(a, SC_CAND_NB);
-  const int32_t* pt = scan_ptr<int32_t>(a, SC_CAND_POINT);
-  const int ended = e.H[H_ENDED], cur = e.H[H_CUR], view = e.H[H_VIEW];
-  const int c0 = cs[cur];
-  const int view_base = t * (B * WT + B), fused_base = view_base + B * WT;      // store.advance(B, te.WT)
   if (tid == 0) {
-    if (!ended) e.H[H_LIVE] += 1;
-    // panorama_inputs: the candidates' views, then the views no candidate used
-    const int fr = scan_ptr<int32_t>(a, SC_FEATURE_ROW)[cur];
-    const int ncand = cs[cur + 1] - c0;
-    uint64_t used = 0;
-    int len = 0;
-    for (int c = 0; c < ncand; ++c) {
-      if (len < W) S[L.o_rows + len] = fr * 36 + pt[c0 + c];
-      used |= (uint64_t)1 << pt[c0 + c];
-      ++len;
-    }
-    for (int k = 0; k < 36; ++k)
-      if (!((used >> k) & 1)) {
-        if (len < W) S[L.o_rows + len] = fr * 36 + k;
-        ++len;
-      }
-    if (len > W) {
-      e.fail(ST_PANO, t);
-      len = W;
-    }
-    e.H[H_VLEN] = len;
-    e.H[H_NCAND] = ncand < W ? ncand : W;
-    if (O > 0) {      // the objects of the viewpoint: contiguous rows of ObjectStore.table
-      const int32_t* os = obj_ptr<int32_t>(a, OB_START);
-      int olen = os[cur + 1] - os[cur];
-      if (olen > O) {
-        e.fail(ST_OBJ, t);
-        olen = O;
-      }
-      e.H[H_OLEN] = olen;
-    }
-    // note_step (nav_inputs.py:233-243)
-    const int n = e.H[H_N];
-    for (int i = 0; i < n; ++i) S[L.o_iscand + i] = 0;
-    const int ci = e.find(cur);
-    if (!ended && ci >= 0) {
-      S[L.o_step + ci] = t + 1;
-      S[L.o_kind + ci] = KIND_SET;
-      S[L.o_nacc + ci] = 1;
-      e.Sb[L.o_acc + ci * L.acc] = fused_base + b;
-    }
-    for (int c = 0; c < e.H[H_NCAND]; ++c) {
-      const int j = e.find(nb[c0 + c]);
-      S[L.o_cnode + c] = j;
-      if (j < 0) continue;
-      S[L.o_iscand + j] = 1;
-      if (!ended && !S[L.o_vis + j]) {            // NodeEmbedStore.accumulate
-        const int row = view_base + b * WT + c;
-        int32_t* acc = e.Sb + L.o_acc + j * L.acc;
-        if (S[L.o_kind + j] == KIND_NONE) {
-          S[L.o_kind + j] = KIND_ACC;
-          S[L.o_nacc + j] = 1;
-          acc[0] = row;
-        } else if (S[L.o_nacc + j] < L.acc) {
-          S[L.o_kind + j] = KIND_ACC;
-          acc[S[L.o_nacc + j]++] = row;
-        } else {
-          e.fail(ST_PATH, t);
-        }
-      }
-    }
-    // gmap_order: [stop], [MEM], the visited nodes, the unvisited ones, each in insertion order
-    int nv = 0;
-    for (int i = 0; i < n; ++i)
-      if (S[L.o_vis + i]) S[L.o_ord + nv++] = i;
-    int nu = nv;
-    for (int i = 0; i < n; ++i)
-      if (!S[L.o_vis + i]) S[L.o_ord + nu++] = i;
-    for (int k = 0; k < n; ++k) S[L.o_slot + S[L.o_ord + k]] = k + 2;
-    e.H[H_NOLEFT] = nu == nv;
-    int nslots = n + 2;
-    if (nslots > G) {
-      e.fail(ST_MAP, t);
-      nslots = G;
-    }
-    e.H[H_NSLOT] = nslots;
-    // teacher_action(imitation_learning=False) (nav_inputs.py:205-218): strict <, the first minimum wins
-    int64_t target = a.ignoreid;
-    if (!ended) {
-      const int goal = e.H[H_GOAL];
-      if (cur == goal) {
-        target = 0;
-      } else {
-        const int s = e.H[H_SCAN];
-        const int off = scan_ptr<int32_t>(a, SC_SCAN_OFF)[s], ns = scan_ptr<int32_t>(a, SC_SCAN_N)[s];
-        const double* dist = scan_ptr<double>(a, SC_DIST) + scan_ptr<int64_t>(a, SC_DIST_OFF)[s];
-        double best = INFINITY;
-        for (int g = 2; g < nslots; ++g) {
-          const int node = S[L.o_ord + g - 2];
-          if (S[L.o_vis + node]) continue;
-          const int k = S[L.o_vp + node] - off;
-          const double d = dist[(int64_t)k * ns + (goal - off)] + dist[(int64_t)(cur - off) * ns + k];
-          if (d < best) {
-            best = d;
-            target = g;
-          }
-        }
-      }
-    }
-    step_ptr<int64_t>(a, TB_TARGET)[b] = target;
-    step_ptr<int64_t>(a, TB_VIEW_LENS)[b] = len;
-    if (O > 0) {
-      // teacher_object (nav_inputs.py:175-186): on one of the episode's end viewpoints the slot of the target object among [stop],
-      // [MEM], the views and the objects; the ignore value elsewhere and where the target is not among the viewpoint's objects
-      const int olen = e.H[H_OLEN];
-      int64_t ot = a.ignoreid;
-      if (!ended) {
-        const int32_t* goal = a.goal + (int64_t)b * a.max_end * 2;
-        for (int k = 0; k < a.max_end; ++k)
-          if (goal[2 * k] == cur) {         // (a viewpoint listed twice carries the same index)
-            const int j = goal[2 * k + 1];
-            if (j >= 0 && j < olen) ot = j + len + 2;
-            break;
-          }
-      }
-      ostep_ptr<int64_t>(a, OT_OBJ_TARGET)[b] = ot;
-      ostep_ptr<int64_t>(a, OT_OBJ_LENS)[b] = olen;
-    }
-    // the episode's share of the node-embedding CSR (NodeEmbedStore.csr): tokens per slot as a running sum
-    int tok = 0;
-    S[L.o_seg] = 0;
-    for (int g = 0; g < G; ++g) {
-      int cnt = 0;
-      if (g == 1 && t > 0) cnt = 1;
-      else if (g >= 2 && g < nslots) cnt = S[L.o_nacc + S[L.o_ord + g - 2]];
-      tok += cnt;
-      S[L.o_seg + g + 1] = tok;
-    }
+    if (!e.H[H_ENDED]) e.H[H_LIVE] += 1;
+    pano_order(a, e, b);
+    note_step(a, e, b);
+    map_order(a, e);
+    teacher_labels(a, e, b);
   }
   sync();
-  const int vlen = e.H[H_VLEN], ncand = e.H[H_NCAND], nslots = e.H[H_NSLOT], n = e.H[H_N];
   const double* vang = scan_ptr<double>(a, SC_VIEW_ANG);
-  const double bh = vang[view * 2], be = vang[view * 2 + 1];
-  // ---- panorama tokens
-  {
-    const double* cang = scan_ptr<double>(a, SC_CAND_ANG);
-    const float* vaf = scan_ptr<float>(a, SC_VAF);
-    const int fr36 = scan_ptr<int32_t>(a, SC_FEATURE_ROW)[cur] * 36;
-    float* loc = step_ptr<float>(a, TB_LOC_FTS) + (int64_t)b * WT * C;
-    int64_t* ty = step_ptr<int64_t>(a, TB_NAV_TYPES) + (int64_t)b * WT;
-    uint8_t* vm = step_ptr<uint8_t>(a, TB_VP_MASK) + (int64_t)b * (WT + 2);
-    uint8_t* vn = step_ptr<uint8_t>(a, TB_VP_NAV) + (int64_t)b * (WT + 2);
-    const int olen = O > 0 ? e.H[H_OLEN] : 0;
-    const int o0 = O > 0 ? obj_ptr<int32_t>(a, OB_START)[cur] : 0;
-    for (int j = tid; j < WT; j += nt) {
-      float* row = loc + j * C;
-      if (j >= vlen && j < vlen + olen) {
-        // ObjectStore.attributes: the object tokens follow the views (nav type 2): [angle_feature(direction - base) | box]
-        const double* dir = obj_ptr<double>(a, OB_DIR) + (int64_t)(o0 + j - vlen) * 2;
-        const float* box = obj_ptr<float>(a, OB_BOX) + (int64_t)(o0 + j - vlen) * 3;
-        angle_row(row, A, dir[0] - bh, dir[1] - be);
-        for (int x = 0; x < 3; ++x) row[A + x] = box[x];
-        ty[j] = 2;
-        continue;
-      }
-      if (j < ncand) {
-        angle_row(row, A, cang[(c0 + j) * 2] - bh, cang[(c0 + j) * 2 + 1] - be);
-      } else if (j < vlen) {
-        const float* src = vaf + ((int64_t)view * 36 + (S[L.o_rows + j] - fr36)) * A;
-        for (int x = 0; x < A; ++x) row[x] = src[x];
-      } else {
-        for (int x = 0; x < A; ++x) row[x] = 0.0f;
-      }
-      for (int x = A; x < C; ++x) row[x] = j < vlen ? 1.0f : 0.0f;
-      ty[j] = j < ncand ? 1 : 0;
-    }
-    for (int j = tid; j < WT + 2; j += nt) {
-      vm[j] = j < vlen + olen + 2;
-      vn[j] = j == 0 ? 1 : (j == 1 ? 0 : (j - 2 < ncand));
-    }
-    if (O > 0) {
-      uint8_t* vo = ostep_ptr<uint8_t>(a, OT_VP_OBJ) + (int64_t)b * (WT + 2);
-      int64_t* names = ostep_ptr<int64_t>(a, OT_OBJ_NAMES) + (int64_t)b * O;
-      const int64_t* name = obj_ptr<int64_t>(a, OB_NAME);
-      // vp_inputs: the head of vp_nav_masks ([stop] true, [MEM] false), then nav_types == 2
-      for (int j = tid; j < WT + 2; j += nt) vo[j] = j == 0 ? 1 : (j - 2 >= vlen && j - 2 < vlen + olen);
-      for (int j = tid; j < O; j += nt) names[j] = j < olen ? name[o0 + j] : 0;
-    }
-  }
-  // ---- map tokens (gmap_inputs, GraphMap.get_pos_fts / pair_dists)
-  {
-    const double* pos = scan_ptr<double>(a, SC_POS);
-    const int32_t* P = e.Sb + L.o_P;
-    int64_t* sid = step_ptr<int64_t>(a, TB_STEP_IDS) + (int64_t)b * G;
-    uint8_t* vmask = step_ptr<uint8_t>(a, TB_VISITED) + (int64_t)b * G;
-    uint8_t* gmask = step_ptr<uint8_t>(a, TB_GMASK) + (int64_t)b * G;
-    float* scale = step_ptr<float>(a, TB_CSR_SCALE) + (int64_t)b * G;
-    float* gp = step_ptr<float>(a, TB_GMAP_POS) + (int64_t)b * G * C;
-    const int ci = e.find(cur);
-    const double ax = pos[cur * 3], ay = pos[cur * 3 + 1], az = pos[cur * 3 + 2];
-    for (int g = tid; g < G; g += nt) {
-      float* row = gp + g * C;
-      const bool real = g >= 2 && g < nslots;
-      const int node = real ? S[L.o_ord + g - 2] : -1;
-      sid[g] = real ? S[L.o_step + node] : 0;
-      vmask[g] = g == 1 ? 1 : (real ? S[L.o_vis + node] != 0 : 0);
-      gmask[g] = g < nslots && (g != 1 || O > 0);      // (gmap_inputs(mem_selectable=has_obj): the REVERIE builder keeps [MEM])
-      scale[g] = (real && S[L.o_kind + node] == KIND_ACC) ? (float)(1.0 / (double)S[L.o_nacc + node]) : 1.0f;
-      if (g >= nslots) {
-        for (int x = 0; x < C; ++x) row[x] = 0.0f;
-        continue;
-      }
-      float h32 = 0.0f, e32 = 0.0f;
-      double line = 0.0, md = 0.0, hops = 0.0;
-      if (real) {
-        const int v = S[L.o_vp + node];
-        const double by = pos[v * 3 + 1];
-        const double dx = pos[v * 3] - ax, dy = by - ay, dz = pos[v * 3 + 2] - az;       // navsim.rel_pos
-        const double xy = fmax(sqrt(dx * dx + dy * dy), 1e-8);
-        const double xyz = fmax(sqrt(dx * dx + dy * dy + dz * dz), 1e-8);
-        double hd = asin(dx / xy);
-        if (by < ay) hd = 3.141592653589793 - hd;
-        const double el = asin(dz / xyz);
-        h32 = (float)(hd - bh);
-        e32 = (float)(el - be);
-        line = xyz / 30.0;
-        if (ci >= 0 && node != ci) {
-          md = e.D[ci * cap + node] / 30.0;
-          int32_t stk[256];
-          const int nh = expand_path(P, cap, ci, node, stk, 256, [](int) {});
-          hops = (double)(nh < 0 ? 0 : nh) / 10.0;
-        }
-      }
-      // get_angle_fts: sin / cos of the float32 angles
-      const float f[4] = {(float)sin((double)h32), (float)cos((double)h32), (float)sin((double)e32), (float)cos((double)e32)};
-      for (int x = 0; x < A; ++x) row[x] = f[x % 4];
-      row[A] = (float)line;
-      row[A + 1] = (float)md;
-      row[A + 2] = (float)hops;
-    }
-    float* pair = step_ptr<float>(a, TB_PAIR) + (int64_t)b * G * G;
-    for (int x = tid; x < G * G; x += nt) {
-      const int g = x / G, h = x % G;
-      float v = 0.0f;
-      if (g >= 2 && h >= 2 && g < nslots && h < nslots && g != h) v = (float)e.D[S[L.o_ord + g - 2] * cap + S[L.o_ord + h - 2]];
-      pair[x] = v;
-    }
-    // nav_fusion_matrix (nav_model.py:231-253)
-    float* fus = step_ptr<float>(a, TB_FUSION) + (int64_t)b * G * (WT + 2);
-    for (int x = tid; x < G * (WT + 2); x += nt) {
-      const int g = x / (WT + 2), j = x % (WT + 2);
-      float v = 0.0f;
-      if (g >= 2 && g < nslots && j >= 2 && j - 2 < ncand) {
-        const int node = S[L.o_ord + g - 2], cn = S[L.o_cnode + j - 2];
-        if (!S[L.o_vis + node] && cn >= 0) {
-          if (cn == node) v = 1.0f;
-          else if (S[L.o_vis + cn] && !S[L.o_iscand + node]) v = 1.0f;
-        }
-      }
-      fus[x] = v;
-    }
-  }
+  const double bh = vang[e.H[H_VIEW] * 2], be = vang[e.H[H_VIEW] * 2 + 1];
+  pano_tokens(a, e, b, bh, be, tid, nt);
+  map_tokens(a, e, b, bh, be, tid, nt);
   sync();
-  // ---- vp_inputs: the start node's row in every slot, the candidates' rows behind it (rows of gmap_pos_fts)
-  {
-    const float* gp = step_ptr<float>(a, TB_GMAP_POS) + (int64_t)b * G * C;
-    float* vp = step_ptr<float>(a, TB_VP_POS) + (int64_t)b * (WT + 2) * 2 * C;
-    const int sn = e.find(e.H[H_START]);
-    const int sslot = sn >= 0 ? S[L.o_slot + sn] : G;
-    for (int x = tid; x < (WT + 2) * 2 * C; x += nt) {
-      const int j = x / (2 * C), c = x % (2 * C);
-      float v = 0.0f;
-      if (c < C) {
-        if (sslot < nslots) v = gp[sslot * C + c];
-      } else if (j >= 2 && j - 2 < ncand) {
-        const int cn = S[L.o_cnode + j - 2];
-        const int slot = cn >= 0 ? S[L.o_slot + cn] : G;
-        if (slot < nslots) v = gp[slot * C + c - C];
-      }
-      vp[x] = v;
-    }
-  }
-  (void)n;
+  vp_tokens(a, e, b, tid, nt);
 }
 
 // One step of one episode: the move of step t - 1, then the tables of step t.
@@ -673,18 +737,28 @@ NAV_HD inline void step_episode(const Args& a, int b, int tid, int nt, Sync sync
   }
 }
 
+// episodes.py:_compact_rows for slot s of a [B, width] table: row j of an episode whose `len` real rows lie from `base` on.  The slot's
+// start, the index `row` of a real row where it lands, and -1 in idx behind the `total` rows of the batch (NO_FILL: the caller's).  -> there
+constexpr int NO_FILL = 0x7fffffff;
+NAV_HD inline int compact_row(int32_t* start, int32_t* idx, int s, int base, int j, int len, int row, int total) {
+  const int at = base + (j < len ? j : len);
+  start[s] = at;
+  if (j < len) idx[at] = row;
+  if (s >= total) idx[s] = -1;
+  return at;
+}
+
 // The batch-wide tail of a step: the compact CSRs are prefix sums over the episodes (episodes.py:_compact_rows, NodeEmbedStore.csr,
-// graphmap.inverse_index).  One group of threads; `part` holds nt ints they share.  ws: [2 * (B + 1)] bases, one owner per pool row, the live count and,
-// with objects, [B + 1] object bases behind it.
+// graphmap.inverse_index).  One group of threads; `part` holds nt ints they share.  ws: the ints of Workspace.
 template <class Sync>
 NAV_HD inline void nav_tail(const Args& a, int32_t* part, int tid, int nt, Sync sync) {
   const int B = a.B, G = a.G, W = a.W, t = a.t, O = a.O, WT = a.W + a.O;
   const int rows = (t + 1) * (B * WT + B), n_src = rows + (t > 0 ? B : 0);
-  const int live_at = 2 * (B + 1) + a.T * (B * WT + B) + B;
-  int32_t* obase = a.ws + live_at + 1;      // object walks: [B + 1] behind the live count
-  int32_t* fbase = a.ws;
-  int32_t* cbase = a.ws + B + 1;
-  int32_t* owner = a.ws + 2 * (B + 1);
+  const Workspace ws(B, a.T, W, O);
+  int32_t* obase = a.ws + ws.obase;      // object walks: [B + 1] behind the live count
+  int32_t* fbase = a.ws + ws.fbase;
+  int32_t* cbase = a.ws + ws.cbase;
+  int32_t* owner = a.ws + ws.owner;
   int32_t* feat_idx = step_ptr<int32_t>(a, TB_FEAT_IDX);
   int32_t* feat_start = step_ptr<int32_t>(a, TB_FEAT_START);
   int32_t* csr_idx = step_ptr<int32_t>(a, TB_CSR_IDX);
@@ -710,7 +784,7 @@ NAV_HD inline void nav_tail(const Args& a, int32_t* part, int tid, int nt, Sync 
     fbase[B] = f;
     cbase[B] = c;
     if (O > 0) obase[B] = o;
-    a.ws[live_at] = live;      // episodes still walking when step t begins (an optional host read)
+    a.ws[ws.live_at] = live;      // episodes still walking when step t begins (an optional host read)
   }
   for (int r = tid; r < n_src; r += nt) owner[r] = -1;
   sync();
@@ -718,10 +792,7 @@ NAV_HD inline void nav_tail(const Args& a, int32_t* part, int tid, int nt, Sync 
   for (int s = tid; s < B * W; s += nt) {
     const int b = s / W, j = s % W;
     Ep e(a, b);
-    const int vl = e.H[H_VLEN];
-    feat_start[s] = fbase[b] + (j < vl ? j : vl);
-    if (j < vl) feat_idx[fbase[b] + j] = e.S[e.L.o_rows + j];
-    if (s >= ftot) feat_idx[s] = -1;
+    compact_row(feat_start, feat_idx, s, fbase[b], j, e.H[H_VLEN], e.S[e.L.o_rows + j], ftot);
   }
   if (tid == 0) {
     feat_start[B * W] = ftot;
@@ -743,32 +814,21 @@ NAV_HD inline void nav_tail(const Args& a, int32_t* part, int tid, int nt, Sync 
     for (int s = tid; s < B * O; s += nt) {
       const int b = s / O, j = s % O;
       Ep e(a, b);
-      const int ol = e.H[H_OLEN], at = obase[b] + (j < ol ? j : ol);
-      obj_start[s] = at;
-      cinv_start[B * W + s] = ftot + at;
-      if (j < ol) {
-        obj_idx[at] = orow[e.H[H_CUR]] + j;
-        cinv_idx[ftot + at] = b * WT + e.H[H_VLEN] + j;
-      }
-      if (s >= otot) obj_idx[s] = -1;
+      const int ol = e.H[H_OLEN];
+      compact_row(obj_start, obj_idx, s, obase[b], j, ol, orow[e.H[H_CUR]] + j, otot);
+      compact_row(cinv_start + B * W, cinv_idx, s, ftot + obase[b], j, ol, b * WT + e.H[H_VLEN] + j, NO_FILL);
     }
     for (int s = tid; s < B * W; s += nt) {
       const int b = s / W, j = s % W;
       Ep e(a, b);
-      const int vl = e.H[H_VLEN], at = fbase[b] + (j < vl ? j : vl);
-      cinv_start[s] = at;
-      if (j < vl) cinv_idx[at] = b * WT + j;
+      compact_row(cinv_start, cinv_idx, s, fbase[b], j, e.H[H_VLEN], b * WT + j, NO_FILL);
     }
     for (int s = tid; s < B * WT; s += nt) {
       const int b = s / WT, j = s % WT;
       Ep e(a, b);
-      const int vl = e.H[H_VLEN], n = vl + e.H[H_OLEN], at = fbase[b] + obase[b] + (j < n ? j : n);
-      cat_start[s] = at;
-      if (j < n) cat_idx[at] = j < vl ? b * W + j : B * W + b * O + (j - vl);
-      if (s >= ttot) {
-        cat_idx[s] = -1;
-        cinv_idx[s] = -1;
-      }
+      const int vl = e.H[H_VLEN];
+      compact_row(cat_start, cat_idx, s, fbase[b] + obase[b], j, vl + e.H[H_OLEN], j < vl ? b * W + j : B * W + b * O + (j - vl), ttot);
+      if (s >= ttot) cinv_idx[s] = -1;
     }
     if (tid == 0) {
       obj_start[B * O] = otot;

@@ -40,24 +40,69 @@ from .navsim import GraphSim, view_angle_feature_table, view_angles
 
 MODES = {'sample': 0, 'argmax': 1, 'forced': 2}
 STATUS = {1: 'the map has more nodes than the bucket of the step holds', 2: 'the panorama is wider than the bucket W',
-          3: 'the action is not a selectable node of the map', 4: 'the hop log or a path stack overflowed'}
+          3: 'the action is not a selectable node of the map', 4: 'the hop log or a path stack overflowed',
+          5: 'the viewpoint has more objects than the bucket obj_width'}
 # the order of the address tables (csrc/navstate_core.hpp)
 SCAN_TABLES = ('pos', 'cand_start', 'cand_nb', 'cand_point', 'cand_ang', 'cand_len', 'feature_row', 'vp_scan', 'scan_off', 'scan_n',
                'dist_off', 'dist', 'vaf', 'view_ang', 'pred')
-STEP_TABLES = (('feat_idx', torch.int32), ('feat_start', torch.int32), ('loc_fts', torch.float32), ('nav_types', torch.int64),
-               ('view_lens', torch.int64), ('gmap_step_ids', torch.int64), ('gmap_pos_fts', torch.float32), ('gmap_pair_dists', torch.float32),
-               ('gmap_visited_masks', torch.bool), ('gmap_masks', torch.bool), ('vp_pos_fts', torch.float32), ('vp_masks', torch.bool),
-               ('vp_nav_masks', torch.bool), ('nav_fusion', torch.float32), ('target', torch.int64), ('csr_idx', torch.int32),
-               ('csr_start', torch.int32), ('csr_scale', torch.float32), ('inv_idx', torch.int32), ('inv_start', torch.int32),
-               ('inv_w', torch.float32))
-H_ENDED, H_STATUS, H_STATUS_T, H_LIVE, H_HOPN, H_BT_START, H_BT_N, H_PRED_VP, H_PRED_OBJ, HDR = 2, 5, 6, 11, 16, 17, 18, 22, 23, 32
+OBJECT_TABLES = ('obj_start', 'obj_row', 'obj_dir', 'obj_box', 'obj_name')
+# the header words of an episode's read-back block, in the order of the enum H_* of csrc/navstate_core.hpp: H[name] is the word's index
+HEADER = ('cur', 'view', 'ended', 'just', 'n', 'status', 'status_t', 'start', 'goal', 'noleft', 'nscored', 'live', 'nslot', 'vlen', 'ncand',
+          'startview', 'hopn', 'bt_start', 'bt_n', 'k', 'scan', 'fold', 'pred_vp', 'pred_obj', 'olen')
+H = {name: i for i, name in enumerate(HEADER)}
+HDR = 32
 MAX_B, MAX_T, MAX_G, MAX_W, MAX_CAP, MAX_REF = 1024, 64, 256, 64, 254, 64        # GOAT_NAV_MAX_* (include/goat_hip.h)
 MAX_O, MAX_END = 64, 64
-STATUS[5] = 'the viewpoint has more objects than the bucket obj_width'
-OBJECT_TABLES = ('obj_start', 'obj_row', 'obj_dir', 'obj_box', 'obj_name')
-OBJECT_STEP_TABLES = (('obj_idx', torch.int32), ('obj_start', torch.int32), ('reverie_obj_lens', torch.int64), ('reverie_obj_names', torch.int64),
-                      ('vp_obj_masks', torch.bool), ('obj_target', torch.int64), ('ocat_idx', torch.int32), ('ocat_start', torch.int32),
-                      ('ocat_inv_idx', torch.int32), ('ocat_inv_start', torch.int32))
+_i32, _i64, _f32, _bool = torch.int32, torch.int64, torch.float32, torch.bool
+# the tables of one step that the kernels write, in the order of their address tables: (name, dtype, shape) with the shape a function of
+# B episodes, the step's map width G, W views and O object slots per panorama, C = A + 3 columns and n pool rows up to the step.  The
+# first 21 are those of every walk (`step_tab`), the ten behind them those of an object walk (`ostep_tab`).
+STEP_SPEC = (
+    ('feat_idx', _i32, lambda B, G, W, O, C, n: (B * W,)), ('feat_start', _i32, lambda B, G, W, O, C, n: (B * W + 1,)),
+    ('loc_fts', _f32, lambda B, G, W, O, C, n: (B, W + O, C)), ('nav_types', _i64, lambda B, G, W, O, C, n: (B, W + O)),
+    ('view_lens', _i64, lambda B, G, W, O, C, n: (B,)), ('gmap_step_ids', _i64, lambda B, G, W, O, C, n: (B, G)),
+    ('gmap_pos_fts', _f32, lambda B, G, W, O, C, n: (B, G, C)), ('gmap_pair_dists', _f32, lambda B, G, W, O, C, n: (B, G, G)),
+    ('gmap_visited_masks', _bool, lambda B, G, W, O, C, n: (B, G)), ('gmap_masks', _bool, lambda B, G, W, O, C, n: (B, G)),
+    ('vp_pos_fts', _f32, lambda B, G, W, O, C, n: (B, W + O + 2, 2 * C)), ('vp_masks', _bool, lambda B, G, W, O, C, n: (B, W + O + 2)),
+    ('vp_nav_masks', _bool, lambda B, G, W, O, C, n: (B, W + O + 2)), ('nav_fusion', _f32, lambda B, G, W, O, C, n: (B, G, W + O + 2)),
+    ('target', _i64, lambda B, G, W, O, C, n: (B,)), ('csr_idx', _i32, lambda B, G, W, O, C, n: (n,)),
+    ('csr_start', _i32, lambda B, G, W, O, C, n: (B * G + 1,)), ('csr_scale', _f32, lambda B, G, W, O, C, n: (B * G,)),
+    ('inv_idx', _i32, lambda B, G, W, O, C, n: (n,)), ('inv_start', _i32, lambda B, G, W, O, C, n: (n + 1,)),
+    ('inv_w', _f32, lambda B, G, W, O, C, n: (n,)),
+    ('obj_idx', _i32, lambda B, G, W, O, C, n: (B * O,)), ('obj_start', _i32, lambda B, G, W, O, C, n: (B * O + 1,)),
+    ('reverie_obj_lens', _i64, lambda B, G, W, O, C, n: (B,)), ('reverie_obj_names', _i64, lambda B, G, W, O, C, n: (B, O)),
+    ('vp_obj_masks', _bool, lambda B, G, W, O, C, n: (B, W + O + 2)), ('obj_target', _i64, lambda B, G, W, O, C, n: (B,)),
+    ('ocat_idx', _i32, lambda B, G, W, O, C, n: (B * (W + O),)), ('ocat_start', _i32, lambda B, G, W, O, C, n: (B * (W + O) + 1,)),
+    ('ocat_inv_idx', _i32, lambda B, G, W, O, C, n: (B * (W + O),)), ('ocat_inv_start', _i32, lambda B, G, W, O, C, n: (B * W + B * O + 1,)))
+N_STEP = 21
+STEP_TABLES = tuple((name, dtype) for name, dtype, _ in STEP_SPEC[:N_STEP])
+OBJECT_STEP_TABLES = tuple((name, dtype) for name, dtype, _ in STEP_SPEC[N_STEP:])
+
+
+def workspace(B, T, W, O=0):
+    """the tail's workspace as `Workspace` of csrc/navstate_core.hpp lays it out -> (its size in ints, the index of the live count)"""
+    live_at = 2 * (B + 1) + T * (B * (W + O) + B) + B
+    return live_at + 1 + (B + 1 if O else 0), live_at
+
+
+class _Staging:
+    """What begin() hands to the device in one copy: `fields` [(name, torch dtype, shape)] laid out one behind the other in a pinned host
+    buffer and its device twin.  host[name] / dev[name]: the numpy / device views of a field."""
+
+    def __init__(self, fields, device):
+        at, n = {}, 0
+        for name, dtype, shape in fields:
+            at[name] = (n, n + int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size())
+            n = at[name][1]
+        self.pinned = torch.zeros(n, dtype=torch.uint8)
+        if device.type == 'cuda':
+            self.pinned = self.pinned.pin_memory()
+        self.device = torch.zeros(n, dtype=torch.uint8, device=device)
+        self.host = {name: self.pinned[slice(*at[name])].view(dtype).view(shape).numpy() for name, dtype, shape in fields}
+        self.dev = {name: self.device[slice(*at[name])].view(dtype).view(shape) for name, dtype, shape in fields}
+
+    def upload(self):
+        self.device.copy_(self.pinned, non_blocking=True)
 
 
 def _pack(host, names, device):
@@ -251,29 +296,20 @@ class DeviceNavigator:
                 raise ValueError('DeviceNavigator: obj_width = %d, max_end = %d outside what goat_nav_obj_step holds (1..%d, 1..%d)'
                                  % (O, max_end, MAX_O, MAX_END))
         WT = self.WT = W + O
-        C = self.A + 3
-        rows = lambda t: (t + 1) * (B * WT + B) + (B if t > 0 else 0)
         self._step_tensors = []
         ptrs, optrs = [], []
         for t in range(T):
-            G, n = self.gw[t], rows(t)
-            want = {'feat_idx': (B * W,), 'feat_start': (B * W + 1,), 'loc_fts': (B, WT, C), 'nav_types': (B, WT), 'view_lens': (B,), 'gmap_step_ids': (B, G),
-                    'gmap_pos_fts': (B, G, C), 'gmap_pair_dists': (B, G, G), 'gmap_visited_masks': (B, G), 'gmap_masks': (B, G),
-                    'vp_pos_fts': (B, WT + 2, 2 * C), 'vp_masks': (B, WT + 2), 'vp_nav_masks': (B, WT + 2), 'nav_fusion': (B, G, WT + 2), 'target': (B,),
-                    'csr_idx': (n,), 'csr_start': (B * G + 1,), 'csr_scale': (B * G,), 'inv_idx': (n,), 'inv_start': (n + 1,), 'inv_w': (n,),
-                    'obj_idx': (B * O,), 'obj_start': (B * O + 1,), 'reverie_obj_lens': (B,), 'reverie_obj_names': (B, O), 'vp_obj_masks': (B, WT + 2),
-                    'obj_target': (B,), 'ocat_idx': (B * WT,), 'ocat_start': (B * WT + 1,), 'ocat_inv_idx': (B * WT,),
-                    'ocat_inv_start': (B * W + B * O + 1,)}
+            n = (t + 1) * (B * WT + B) + (B if t > 0 else 0)
             ts = []
-            for name, dtype in STEP_TABLES + (OBJECT_STEP_TABLES if O else ()):
-                v = t_.get('s%d_%s' % (t, name))
-                if v is None or tuple(v.shape) != want[name] or v.dtype != dtype:
+            for name, dtype, shape in STEP_SPEC if O else STEP_SPEC[:N_STEP]:
+                v, want = t_.get('s%d_%s' % (t, name)), shape(B, self.gw[t], W, O, self.A + 3, n)
+                if v is None or tuple(v.shape) != want or v.dtype != dtype:
                     raise ValueError('DeviceNavigator: s%d_%s is %s, the navigator writes %s %s' % (
-                        t, name, None if v is None else (tuple(v.shape), v.dtype), want[name], dtype))
+                        t, name, None if v is None else (tuple(v.shape), v.dtype), want, dtype))
                 ts.append(v)
             self._step_tensors.append(ts)
-            ptrs.append([v.data_ptr() for v in ts[:len(STEP_TABLES)]])
-            optrs.append([v.data_ptr() for v in ts[len(STEP_TABLES):]])
+            ptrs.append([v.data_ptr() for v in ts[:N_STEP]])
+            optrs.append([v.data_ptr() for v in ts[N_STEP:]])
         h = _lib.lib()
         self.state_ints = h.goat_nav_obj_state_ints(T, W, O, self.cap) if O else h.goat_nav_state_ints(T, W, self.cap)
         self.log_ints = h.goat_nav_log_ints(T, self.cap)
@@ -285,34 +321,27 @@ class DeviceNavigator:
         self.si = torch.zeros(B * self.state_ints, dtype=torch.int32, device=dev)
         self.sd = torch.zeros(B * (self.cap * self.cap + self.cap), dtype=torch.float64, device=dev)
         self.log = torch.zeros(2 * T * B + B * self.log_ints, dtype=torch.int32, device=dev)
-        self._live_at = 2 * (B + 1) + T * (B * WT + B) + B
-        self.ws = torch.zeros(self._live_at + 1 + (B + 1 if O else 0), dtype=torch.int32, device=dev)
-        # staging of begin(): [u float64 [T, B] | ep int32 [B, 4] | forced actions int32 [T, B]] and, for the nDTW expert, behind them
-        # [ground-truth paths int32 [B, max_ref + 1]: length, viewpoint numbers]; for an object walk [goals int32 [B, max_end, 2]]
-        self._n_u, self._n_ep = T * B * 8, B * 4 * 4
-        self._n_forced = T * B * 4
+        ws_ints, self._live_at = workspace(B, T, W, O)
+        self.ws = torch.zeros(ws_ints, dtype=torch.int32, device=dev)
+        # staging of begin(): the uniforms, (scan, start viewpoint, start view, goal) per episode, the forced actions; for the nDTW
+        # expert the ground-truth paths (length, viewpoint numbers) and for an object walk the goals behind them
         ndtw = self.expert == 'ndtw'
-        nbytes = self._n_u + self._n_ep + self._n_forced + (B * (max_ref + 1) * 4 if ndtw else 0) + (B * max_end * 2 * 4 if O else 0)
-        self._stage = torch.zeros(nbytes, dtype=torch.uint8)
+        self._stage = _Staging([('u', torch.float64, (T, B)), ('ep', _i32, (B, 4)), ('forced', _i32, (T, B))]
+                               + ([('ref', _i32, (B, max_ref + 1))] if ndtw else []) + ([('goal', _i32, (B, max_end, 2))] if O else []), dev)
+        d = self._stage.dev
+        self.u, self.ep, self.forced, self.ref, self.goal = d['u'], d['ep'], d['forced'], d.get('ref'), d.get('goal')
         self._log_host = torch.zeros(self.log.numel(), dtype=torch.int32)
         if dev.type == 'cuda':
-            self._stage, self._log_host = self._stage.pin_memory(), self._log_host.pin_memory()
-        self._in = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self.u = self._in[:self._n_u].view(torch.float64).view(T, B)
-        self.ep = self._in[self._n_u:self._n_u + self._n_ep].view(torch.int32).view(B, 4)
-        self.forced = self._in[self._n_u + self._n_ep:self._n_u + self._n_ep + self._n_forced].view(torch.int32).view(T, B)
+            self._log_host = self._log_host.pin_memory()
         self._copied = None
         self.episodes = None
         self.launches_per_step = 2
-        if O:
-            self.goal = self._in[self._n_u + self._n_ep + self._n_forced:].view(torch.int32).view(B, max_end, 2)
         if ndtw:
             # the DTW row of the walked path and one working row per map node: sized by this navigator's cap and max_ref, not by the
             # limits of the ABI (there: 133 KB per episode)
             self.expert_doubles = h.goat_nav_expert_doubles(self.cap, max_ref)
             if self.expert_doubles <= 0:
                 raise RuntimeError('libgoat_hip: goat_nav_expert_doubles(cap=%d, max_ref=%d) gave no size' % (self.cap, max_ref))
-            self.ref = self._in[self._n_u + self._n_ep + self._n_forced:].view(torch.int32).view(B, max_ref + 1)
             self.xd = torch.zeros(B * self.expert_doubles, dtype=torch.float64, device=dev)
             self.launches_per_step = 3
 
@@ -330,10 +359,8 @@ class DeviceNavigator:
         t0 = time.perf_counter()
         if self._copied is not None:
             self._copied.synchronize()              # the previous H2D has read the pinned buffer
-        st = self._stage.numpy()
-        u = st[:self._n_u].view(np.float64).reshape(T, B)
-        ep = st[self._n_u:self._n_u + self._n_ep].view(np.int32).reshape(B, 4)
-        forced = st[self._n_u + self._n_ep:self._n_u + self._n_ep + self._n_forced].view(np.int32).reshape(T, B)
+        st = self._stage.host
+        u, ep, forced = st['u'], st['ep'], st['forced']
         if self.mode == 'sample':
             u[:] = (rng if rng is not None else np.random.RandomState(0)).random_sample((T, B))
         forced[:] = 0
@@ -345,7 +372,7 @@ class DeviceNavigator:
                 raise ValueError('%d recorded steps exceed the episode bucket T = %d' % (len(acts), T))
             forced[:len(acts)] = acts
         if self.expert == 'ndtw':
-            ref = st[self._n_u + self._n_ep + self._n_forced:].view(np.int32).reshape(B, self.max_ref + 1)
+            ref = st['ref']
             for i, e in enumerate(episodes):
                 if not 1 <= len(e['path']) <= self.max_ref:
                     raise ValueError('DeviceNavigator: the ground-truth path of episode %d has %d viewpoints, the bucket max_ref holds 1..%d'
@@ -355,8 +382,7 @@ class DeviceNavigator:
                 ref[i, 0] = len(e['path'])
                 ref[i, 1:1 + len(e['path'])] = [self.tables.vp(e['scan'].name, vp) for vp in e['path']]
         if self.O:
-            goals = object_goals(episodes, self.objects, self.max_end, bool(getattr(te.sim, 'obj_fallback', False)))
-            st[self._n_u + self._n_ep + self._n_forced:].view(np.int32).reshape(B, self.max_end, 2)[:] = goals
+            st['goal'][:] = object_goals(episodes, self.objects, self.max_end, bool(getattr(te.sim, 'obj_fallback', False)))
         for i, e in enumerate(episodes):
             name = e['scan'].name
             ep[i] = (self.tables.ids[name], self.tables.vp(name, e['path'][0]), GraphSim._snap(e['heading'], 0.0), self.tables.vp(name, e['path'][-1]))
@@ -369,7 +395,7 @@ class DeviceNavigator:
             msk = torch.zeros(B, te.L, dtype=torch.bool)
             ids[:, :n], msk[:, :n] = lang['txt_ids'], lang['txt_masks']
             self.bufs.load_part({'txt_ids': ids, 'txt_masks': msk})
-        self._in.copy_(self._stage, non_blocking=True)
+        self._stage.upload()
         if self.device.type == 'cuda':
             self._copied = torch.cuda.Event()
             self._copied.record()
@@ -416,8 +442,8 @@ class DeviceNavigator:
         acts, alive = log[:T * B].reshape(T, B), log[T * B:2 * T * B].reshape(T, B)
         blocks = log[2 * T * B:].reshape(B, self.log_ints)
         for i in range(B):
-            if blocks[i, H_STATUS]:
-                raise ValueError('device navigator: episode %d, step %d: %s' % (i, int(blocks[i, H_STATUS_T]), STATUS.get(int(blocks[i, H_STATUS]), 'status %d' % blocks[i, H_STATUS])))
+            if blocks[i, H['status']]:
+                raise ValueError('device navigator: episode %d, step %d: %s' % (i, int(blocks[i, H['status_t']]), STATUS.get(int(blocks[i, H['status']]), 'status %d' % blocks[i, H['status']])))
         names = self.tables.names
         traj = []
         for i, e in enumerate(self.episodes):
@@ -426,17 +452,17 @@ class DeviceNavigator:
             for t in range(T):
                 if hs[t + 1] > hs[t]:
                     path.append([names[v] for v in hops[hs[t]:hs[t + 1]]])
-            if blocks[i, H_BT_N]:
-                s = int(blocks[i, H_BT_START])
-                path.append([names[v] for v in hops[s:s + int(blocks[i, H_BT_N])]])
+            if blocks[i, H['bt_n']]:
+                s = int(blocks[i, H['bt_start']])
+                path.append([names[v] for v in hops[s:s + int(blocks[i, H['bt_n']])]])
             traj.append({'instr_id': e['instr_id'], 'path': path})
             if self.O and self.mode == 'argmax':        # EpisodePlanner(feedback='argmax'): the best object of the best stop node
-                v, j = int(blocks[i, H_PRED_VP]) - 1, int(blocks[i, H_PRED_OBJ])
+                v, j = int(blocks[i, H['pred_vp']]) - 1, int(blocks[i, H['pred_obj']])
                 traj[-1]['pred_objid'] = self.objects.ids[v][j] if (v >= 0 and j >= 0) else None
         actions = [acts[t].astype(np.int64) for t in range(T) if alive[t].any()]
         self.alive = alive.astype(bool)
         self.host_s += time.perf_counter() - t0
-        return traj, actions, int(blocks[:, H_LIVE].sum()), blocks[:, H_ENDED].astype(bool)
+        return traj, actions, int(blocks[:, H['live']].sum()), blocks[:, H['ended']].astype(bool)
 
     def walk(self, ep, episodes, rng=None, actions=None, act=None, after=None, check_every=None, text='host'):
         """the whole walk over the graphs of `ep` (g_lang, g_step): begin, per step the navigator then the step graph, the last move,
