@@ -85,6 +85,9 @@ int goat_gemm_bf16(void* stream, int trans_a, int trans_b, int dtype_out,
                    const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                    int M, int N, int Kc, const float* bias, int epilogue,
                    void* aux, int64_t ldaux, int split_k, int bm, int nstage, float* colsum);
+/* Does this build have that configuration?  0, or GOAT_E_ARG where goat_gemm_bf16 would refuse the same seven arguments whatever the
+ * operands (tile = its bm argument).  The lookup goat_gemm_bf16 itself performs before it launches; takes no pointer, touches no device. */
+int goat_gemm_bf16_query(int trans_a, int trans_b, int dtype_out, int epilogue, int split_k, int tile, int nstage);
 /* colsum[c] += sum_r x[r,c] (float32, atomic; caller zero-fills): bias gradient of a Linear. */
 int goat_colsum(void* stream, int dtype, const void* x, int64_t ld, int R, int C, float* colsum);
 
@@ -435,6 +438,8 @@ int goat_wgrad_grouped(void* stream, const goat_wgrad_problem* probs, int n, int
 int goat_wgrad_grouped_balanced(void* stream, const goat_wgrad_problem* probs, int n, int bm, void* workspace,
                                 int64_t workspace_bytes);
 int goat_wgrad_balanced_ws_bytes(int bm);   /* < 0: bm is not one of the tiles above */
+/* 0, or GOAT_E_ARG where goat_wgrad_grouped would refuse (bm, nstage) whatever the problems: its own lookup, no pointer, no device. */
+int goat_wgrad_grouped_query(int tile, int nstage);
 
 /* Embedding tables (float32 masters):  out[r,:] = word[ids[r],:] + type[type_ids ? type_ids[r] : 0,:] + pos[r % L,:]
  * cast to `dtype` — the three nn.Embedding lookups and two adds of BertEmbeddings.forward

@@ -58,6 +58,23 @@ def test_refused_runs_are_refused_by_the_entry(h):
     assert wgrad_layout == 18 and n == 5 * 2 * 4 + wgrad_layout * 4          # the persistent loop on two layouts; the weight-gradient layout
 
 
+def test_expected_status_equals_the_query(h):
+    """the GPU suite's table of refusals and the library's own table (goat_gemm_bf16_query) agree on every (configuration, layout, run)"""
+    for bm, ns, ta, tb in gf.GEMM_TABLE:
+        for run in gf.RUNS:
+            f32 = run in ('f32', 'accum', 'split2', 'split3')
+            epi = dict(accum=gf.EPI_ACCUM, gelu=gf.EPI_GELU, relu=gf.EPI_RELU, dgelu=gf.EPI_MUL_DGELU, drelu=gf.EPI_MUL_DRELU).get(run, gf.EPI_NONE)
+            split = int(run[5:]) if run.startswith('split') else 1
+            assert h.goat_gemm_bf16_query(ta, tb, 0 if f32 else 1, epi, split, bm, ns) == gf.expected_status(bm, ns, ta, tb, run), (gf.cfg_name(bm, ns), ta, tb, run)
+
+
+def test_grouped_tables_equal_the_query(h):
+    for bm, ns in gf.GROUPED_CONFIGS:
+        assert h.goat_wgrad_grouped_query(bm, ns) == 0, (hex(bm), hex(ns))
+    for bm, ns in gf.GROUPED_REFUSED:
+        assert h.goat_wgrad_grouped_query(bm, ns) == gf.GOAT_E_ARG, (hex(bm), hex(ns))
+
+
 def test_grouped_refusals_are_refused_by_the_entry(h):
     from vln_goat_amd import _lib
     arr = (_lib.WgradProblem * 1)()

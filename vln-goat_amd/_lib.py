@@ -33,6 +33,7 @@ SIGNATURES = {
     'goat_version': [],
     'goat_gemm_nt': [_vp, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _i32],
     'goat_gemm_bf16': [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp],
+    'goat_gemm_bf16_query': [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
     'goat_colsum': [_vp, _i32, _vp, _i64, _i32, _i32, _vp],
     'goat_transpose': [_vp, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
     'goat_ln_fwd': [_vp, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _i32, _i32],
@@ -78,6 +79,7 @@ SIGNATURES = {
     'goat_wgrad_grouped': [_vp, _vp, _i32, _i32, _i32],
     'goat_wgrad_grouped_balanced': [_vp, _vp, _i32, _i32, _vp, _i64],
     'goat_wgrad_balanced_ws_bytes': [_i32],
+    'goat_wgrad_grouped_query': [_i32, _i32],
     'goat_grad_sqnorm': [_vp, _vp, _vp, _i32, _vp],
     'goat_adamw_step': [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _vp],
     'goat_optim_step': [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp],

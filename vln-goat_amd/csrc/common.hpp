@@ -359,3 +359,19 @@ template <typename F>
 int bool_dispatch(bool flag, F&& f) {
   return flag ? f(std::true_type{}) : f(std::false_type{});
 }
+
+// Launch of a kernel that asks for more dynamic LDS than the 64 KiB a kernel gets by default: raises Kern's limit to `smem` on its first
+// launch, launches, and returns the HIP status (0, or the positive hipError_t).  Kern's launches all pass the same `smem`.  The flag is
+// one per kernel per PROCESS, not per device: a second device in one process would launch without its limit raised.
+template <auto Kern, typename Args>
+int launch_kernel(dim3 grid, dim3 block, int smem, hipStream_t st, const Args& args) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess) return (int)e;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(Kern, grid, block, smem, st, args);
+  GOAT_LAUNCH_CHECK();
+  return 0;
+}

@@ -260,18 +260,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_kernel(GemmArgs p) {
 
 template <typename T, typename OutT, int EPI, bool SPLITK>
 int launch(hipStream_t st, const GemmArgs& a, int split) {
-  auto kern = gemm_nt_kernel<T, OutT, EPI, SPLITK>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  dim3 grid(a.tiles_m * a.tiles_n, SPLITK ? split : 1);
-  hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), SMEM_BYTES, st, a);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return launch_kernel<gemm_nt_kernel<T, OutT, EPI, SPLITK>>(dim3(a.tiles_m * a.tiles_n, SPLITK ? split : 1), dim3(NTHREADS), SMEM_BYTES, st, a);
 }
 
 template <typename T, typename OutT>

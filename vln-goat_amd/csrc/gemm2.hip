@@ -50,33 +50,31 @@ static int pick_group_m(int tiles_m, int tiles_n, int bm, int bn) {
 }
 
 
-// tile = bm | bn << 16 (bn = 0: 128 columns).  4-wave / 128-column tiles live here, the rest in gemm3.hip.
-static bool tile_ok(int bm, int bn, bool eight) {
-  if (bn == 128 && bm == 96) return !eight;
-  if (bn == 128) return bm == 64 || bm == 128 || bm == 256 ? (!eight || bm == 128) : false;
-  if (eight) return false;
-  return (bm == 128 && bn == 256) || (bm == 192 && bn == 256) || (bm == 256 && bn == 192) || (bm == 256 && bn == 256) || (bm == 192 && bn == 192);
+// tile of a LOCKSTEP row of this unit -> type: f(CF{}).  (The other rows: gemm3.hip, gemm5.hip.)
+template <class F>
+static int with_tile(const Row& r, F&& f) {
+  if (is_tile<T64>(r)) return f(T64{});
+  if (is_tile<T256>(r)) return f(T256{});
+  if (is_tile<T128X8>(r)) return f(T128X8{});
+  if (is_tile<T128>(r)) return f(T128{});
+  return GOAT_E_ARG;
 }
+static_assert(unit_covered<T64, T256, T128X8, T128>(goat_tiles::GEMM2), "a table row of this unit has no with_tile arm");
 
-// tiles of the ping-pong main loop: 64*MI x 128*NI, nstage = number of B buffers
-static bool pp_tile_ok(int bm, int bn, int nstage) {
-  return nstage == 2 && ((bm == 256 && bn == 256) || (bm == 192 && bn == 256) || (bm == 128 && bn == 256) || (bm == 256 && bn == 128) || (bm == 128 && bn == 128));
+// Would goat_gemm_bf16 / goat_wgrad_grouped take this configuration?  0 or GOAT_E_ARG: the very lookup the two perform before they launch.
+// No pointers, no device.
+extern "C" int goat_gemm_bf16_query(int trans_a, int trans_b, int dtype_out, int epilogue, int split_k, int tile, int nstage) {
+  return goat_tiles::gemm_row(goat_tiles::decode_request(tile, nstage), trans_a, trans_b, dtype_out, epilogue, split_k) ? 0 : GOAT_E_ARG;
+}
+extern "C" int goat_wgrad_grouped_query(int tile, int nstage) {
+  return goat_tiles::grouped_row(goat_tiles::decode_request(tile, nstage)) ? 0 : GOAT_E_ARG;
 }
 
 extern "C" int goat_gemm_bf16(void* stream, int trans_a, int trans_b, int dtype_out,
                               const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                               int M, int N, int Kc, const float* bias, int epilogue,
-                              void* aux, int64_t ldaux, int split_k, int bm, int nstage, float* colsum) {
+                              void* aux, int64_t ldaux, int split_k, int tile, int nstage, float* colsum) {
   if (!A || !B || !C) return GOAT_E_ARG;
-  const bool eight = (nstage & GOAT_GEMM_8WAVES) != 0;
-  const bool pp = (nstage & GOAT_GEMM_PP) != 0;               // the ping-pong main loop (gemm5_tile.hpp)
-  const bool persist = (nstage & GOAT_GEMM_PERSIST) != 0;     // ... as one workgroup per CU walking the tiles
-  nstage &= ~(GOAT_GEMM_8WAVES | GOAT_GEMM_PP | GOAT_GEMM_PERSIST);
-  if (nstage < 2 || nstage > 4) return GOAT_E_ARG;
-  if (persist && !pp) return GOAT_E_ARG;
-  int bn = (bm >> 16) & 0xFFFF;
-  bm &= 0xFFFF;
-  if (bn == 0) bn = 128;
   if (colsum && !trans_a) return GOAT_E_ARG;
   if (M <= 0 || N <= 0 || Kc <= 0) return GOAT_E_SHAPE;
   if ((lda % 8) || (ldb % 8)) return GOAT_E_SHAPE;
@@ -84,13 +82,14 @@ extern "C" int goat_gemm_bf16(void* stream, int trans_a, int trans_b, int dtype_
   // contraction tails: transposed operands are zero-filled by the bounds check; K-contiguous operands need
   // whole 64-wide tiles (callers route other shapes to goat_gemm_nt)
   if ((!trans_a || !trans_b) && (Kc % BK)) return GOAT_E_SHAPE;
-  if (trans_a && !trans_b) return GOAT_E_ARG;
   // C = (A·B) * act'(aux): no bias.  The shared epilogue (gemm_epilogue.hpp: store_tile_bf16) relies on this rejection — it reads no bias
   // in its x act' instantiations, for any main loop.
   if ((epilogue == GOAT_EPI_MUL_DGELU || epilogue == GOAT_EPI_MUL_DRELU) && (!aux || bias)) return GOAT_E_ARG;
-  if (epilogue == GOAT_EPI_ACCUM && (dtype_out != GOAT_F32 || bias)) return GOAT_E_ARG;
-  if (split_k > 1 && (dtype_out != GOAT_F32 || (epilogue != GOAT_EPI_NONE && epilogue != GOAT_EPI_ACCUM) || bias)) return GOAT_E_ARG;
-  if (pp ? (eight || !pp_tile_ok(bm, bn, nstage)) : !tile_ok(bm, bn, eight)) return GOAT_E_ARG;
+  if ((epilogue == GOAT_EPI_ACCUM || split_k > 1) && bias) return GOAT_E_ARG;      // (both add into a float32 C)
+  const goat_tiles::Request q = goat_tiles::decode_request(tile, nstage);
+  const Row* row = goat_tiles::gemm_row(q, trans_a, trans_b, dtype_out, epilogue, split_k);
+  if (!row) return GOAT_E_ARG;
+  const int bm = row->bm, bn = row->bn;
   const int64_t a_rows = trans_a ? Kc : M, b_rows = trans_b ? Kc : N;
   const int64_t a_bytes = a_rows * lda * 2, b_bytes = b_rows * ldb * 2;
   if (a_bytes >= (1ll << 31) || b_bytes >= (1ll << 31)) return GOAT_E_SHAPE;
@@ -113,26 +112,10 @@ extern "C" int goat_gemm_bf16(void* stream, int trans_a, int trans_b, int dtype_
   // tests/test_gemm_family_gpu.py, Kc = 64 with split_k 2 / 3 onto a base).  float32 C without bias was checked above.
   if (adds_into_c && split_k == 1) a.accum = 1;
   a.k_tiles_per_split = (kt + split_k - 1) / split_k;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (pp) return goat_g5_dispatch(st, a, bm, bn, trans_a, trans_b, dtype_out, epilogue, split_k, nstage, persist);
-  if (bn != 128 || bm == 96) return goat_g3_dispatch(st, a, bm, bn, trans_a, trans_b, dtype_out, epilogue, split_k, nstage);
-  if (bm == 64) return dispatch_layout<T64>(st, a, trans_a, trans_b, dtype_out, epilogue, split_k, nstage);
-  if (bm == 256) return dispatch_layout<T256>(st, a, trans_a, trans_b, dtype_out, epilogue, split_k, nstage);
-  if (eight) return dispatch_layout<T128X8>(st, a, trans_a, trans_b, dtype_out, epilogue, split_k, nstage);
-  return dispatch_layout<T128>(st, a, trans_a, trans_b, dtype_out, epilogue, split_k, nstage);
-}
-
-template <class CF>
-static int group_stages(hipStream_t st, const GroupArgs& g, int nstage) {
-  constexpr int STAGE = smem_bytes<CF, true, true, 1>();
-  if (nstage == 2) return launch_group<CF, 2>(st, g);
-  if constexpr (3 * STAGE <= 160 * 1024) {
-    if (nstage == 3) return launch_group<CF, 3>(st, g);
-  }
-  if constexpr (4 * STAGE <= 160 * 1024 && CF::BM * CF::BN <= 128 * 128) {
-    if (nstage == 4) return launch_group<CF, 4>(st, g);
-  }
-  return GOAT_E_ARG;
+  const GemmCall c = {ST(stream), a, trans_a, trans_b, dtype_out, epilogue, split_k, q.stages};
+  if (row->unit == goat_tiles::GEMM5) return goat_g5_gemm(c, *row);
+  if (row->unit == goat_tiles::GEMM3) return goat_g3_gemm(c, *row);
+  return with_tile(*row, [&](auto cf) { return dispatch_layout<LockstepLoop, decltype(cf)>(c); });
 }
 
 // argument block of a grouped launch from the caller's problem list (validation shared by the two entry points)
@@ -163,42 +146,29 @@ static int build_group(const goat_wgrad_problem* probs, int n, int bm, int bn, G
   return 0;
 }
 
-extern "C" int goat_wgrad_grouped(void* stream, const goat_wgrad_problem* probs, int n, int bm, int nstage) {
+extern "C" int goat_wgrad_grouped(void* stream, const goat_wgrad_problem* probs, int n, int tile, int nstage) {
   if (!probs || n < 1 || n > GROUP_MAX) return GOAT_E_ARG;
-  const bool eight = (nstage & GOAT_GEMM_8WAVES) != 0;       // as in goat_gemm_bf16: the 128-row tile on eight waves
-  const bool pp = (nstage & GOAT_GEMM_PP) != 0;
-  nstage &= ~(GOAT_GEMM_8WAVES | GOAT_GEMM_PP);
-  int bn = (bm >> 16) & 0xFFFF;
-  bm &= 0xFFFF;
-  if (bn == 0) bn = 128;
-  if (nstage < 2 || nstage > 4 || (bm & (bm - 1)) || (bn & (bn - 1))) return GOAT_E_ARG;
-  if (pp ? (eight || !pp_tile_ok(bm, bn, nstage) || (bm == 128 && bn == 128)) : !tile_ok(bm, bn, eight)) return GOAT_E_ARG;
+  const goat_tiles::Request q = goat_tiles::decode_request(tile, nstage);
+  const Row* row = goat_tiles::grouped_row(q);
+  if (!row) return GOAT_E_ARG;
   GroupArgs g;
-  if (int e = build_group(probs, n, bm, bn, g)) return e;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (pp) return goat_g5_group(st, g, bm, bn, nstage);
-  if (bn != 128) return goat_g3_group(st, g, bm, bn, nstage);
-  if (bm == 64) return group_stages<T64>(st, g, nstage);
-  if (bm == 256) return group_stages<T256>(st, g, nstage);
-  if (eight) return group_stages<T128X8>(st, g, nstage);
-  return group_stages<T128>(st, g, nstage);
+  if (int e = build_group(probs, n, row->bm, row->bn, g)) return e;
+  if (row->unit == goat_tiles::GEMM5) return goat_g5_group(ST(stream), g, *row);
+  if (row->unit == goat_tiles::GEMM3) return goat_g3_group(ST(stream), g, *row, q.stages);
+  return with_tile(*row, [&](auto cf) { return launch_group<decltype(cf)>(ST(stream), g, q.stages); });
 }
 
 // Contraction-balanced form of the grouped launch (gemm5_tile.hpp: pp_group_sk_kernel): ping-pong tiles 256x256 / 128x256 / 256x128.
-extern "C" int goat_wgrad_grouped_balanced(void* stream, const goat_wgrad_problem* probs, int n, int bm, void* workspace, int64_t workspace_bytes) {
+extern "C" int goat_wgrad_grouped_balanced(void* stream, const goat_wgrad_problem* probs, int n, int tile, void* workspace, int64_t workspace_bytes) {
   if (!probs || n < 1 || n > GROUP_MAX) return GOAT_E_ARG;
-  int bn = (bm >> 16) & 0xFFFF;
-  bm &= 0xFFFF;
-  if (bn == 0) bn = 128;
-  if (goat_g5_group_sk_ws_bytes(bm, bn) < 0) return GOAT_E_ARG;
+  const Row* row = goat_tiles::balanced_row(goat_tiles::decode_request(tile));
+  if (!row) return GOAT_E_ARG;
   GroupArgs g;
-  if (int e = build_group(probs, n, bm, bn, g)) return e;
-  return goat_g5_group_sk(reinterpret_cast<hipStream_t>(stream), g, bm, bn, 2, workspace, workspace_bytes);
+  if (int e = build_group(probs, n, row->bm, row->bn, g)) return e;
+  return goat_g5_group_sk(ST(stream), g, *row, workspace, workspace_bytes);
 }
 
-extern "C" int goat_wgrad_balanced_ws_bytes(int bm) {
-  int bn = (bm >> 16) & 0xFFFF;
-  bm &= 0xFFFF;
-  if (bn == 0) bn = 128;
-  return (int)goat_g5_group_sk_ws_bytes(bm, bn);       // 256 slots of <= 264 KiB: fits an int
+extern "C" int goat_wgrad_balanced_ws_bytes(int tile) {
+  const Row* row = goat_tiles::balanced_row(goat_tiles::decode_request(tile));
+  return row ? goat_g5_group_sk_ws_bytes(*row) : -1;
 }

@@ -34,6 +34,7 @@
 #include <unordered_map>
 #include <vector>
 #include "gemm_epilogue.hpp"
+#include "gemm_tiles.hpp"
 
 namespace goat_g2 {
 
@@ -62,6 +63,7 @@ struct Cfg {
   static constexpr int WM = WM_, WN = WN_, MI = MI_, NI = NI_;
   static constexpr int NW = WM * WN, NTH = NW * 64;
   static constexpr int BM = 32 * MI * WM, BN = 32 * NI * WN;
+  static constexpr bool EIGHT = BM == 128 && BN == 128 && NW == 8;      // the tile GOAT_GEMM_8WAVES selects
 };
 // tile ids of the C ABI (bm | bn << 16; bn = 0 means 128; GOAT_GEMM_8WAVES in nstage selects the 8-wave 128x128 tile)
 typedef Cfg<2, 2, 1, 2> T64;        //  64 x 128, 4 waves
@@ -142,6 +144,17 @@ __device__ __forceinline__ int xcd_chunk_position(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
+// position in a problem's tile order -> (tile row, tile column).  Tiles are visited column-major within groups of group_m tile rows, so the
+// workgroups an XCD runs at a time (xcd_chunk_position) cover a compact group_m x (n / group_m) block: its A and B panels are fetched into that
+// L2 once, and the 8 XCD chunks form a 2-D partition of C instead of 8 full-width stripes.
+__device__ __forceinline__ void tile_of_position(const G2Args& p, int pos, int& tm, int& tn) {
+  const int gsz = p.group_m * p.tiles_n;
+  const int grp = pos / gsz, gi = pos - grp * gsz;
+  const int gm = min(p.tiles_m - grp * p.group_m, p.group_m);
+  tn = gi / gm;
+  tm = grp * p.group_m + (gi - tn * gm);
+}
+
 template <class CF, bool TA, bool TB, int NSTAGE>
 constexpr int smem_bytes() { return NSTAGE * (Tile<TA, CF::BM>::BYTES + Tile<TB, CF::BN>::BYTES); }
 
@@ -184,14 +197,8 @@ __device__ __forceinline__ void gemm2_tile(const G2Args& p, int bid, int split) 
   const int wm = wave / WN, wn = wave % WN;
   const int hi = lane >> 5, l31 = lane & 31;
 
-  // `bid` walks a contiguous chunk per XCD (each XCD has its own L2).  Inside the chunk tiles are visited
-  // column-major within groups of group_m tile rows, so the workgroups an XCD runs at a time cover a compact
-  // group_m x (n/group_m) block: its A and B panels are fetched into that L2 once, and the 8 XCD chunks form a 2-D
-  // partition of C instead of 8 full-width stripes.
-  const int gsz = p.group_m * p.tiles_n;
-  const int grp = bid / gsz, gi = bid - grp * gsz;
-  const int gm = min(p.tiles_m - grp * p.group_m, p.group_m);
-  const int tn = gi / gm, tm = grp * p.group_m + (gi - tn * gm);
+  int tm, tn;       // `bid` walks a contiguous chunk per XCD (each XCD has its own L2)
+  tile_of_position(p, bid, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
 
   int kt_begin = 0, kt_end = (p.Kc + BK - 1) / BK;
@@ -524,49 +531,57 @@ struct GroupArgs {
   int tile_start[GROUP_MAX + 1];
   int n;
 };
-template <class CF, int NSTAGE>
-__global__ __launch_bounds__(CF::NTH) void gemm2_group_kernel(GroupArgs g) {
-  const int pos = xcd_chunk_position(blockIdx.x, gridDim.x);
+// the problem (of n) that owns position pos, problem i owning [start[i], start[i + 1])
+__device__ __forceinline__ int group_problem_of(const int (&start)[GROUP_MAX + 1], int n, int pos) {
   int pi = 0;
 #pragma unroll
   for (int i = 1; i < GROUP_MAX; ++i)
-    if (i < g.n && pos >= g.tile_start[i]) pi = i;
+    if (i < n && pos >= start[i]) pi = i;
+  return pi;
+}
+template <class CF, int NSTAGE>
+__global__ __launch_bounds__(CF::NTH) void gemm2_group_kernel(GroupArgs g) {
+  const int pos = xcd_chunk_position(blockIdx.x, gridDim.x);
+  const int pi = group_problem_of(g.tile_start, g.n, pos);
   const G2Args p = g.prob[pi].template expand<CF::BM, CF::BN>();
   gemm2_tile<CF, true, true, float, GOAT_EPI_NONE, false, NSTAGE>(p, pos - g.tile_start[pi], 0);
 }
 
-template <class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK, int NSTAGE>
-int launch2s(hipStream_t st, const G2Args& a, int split) {
-  constexpr int SMEM = smem_bytes<CF, TA, TB, NSTAGE>();
-  static_assert(SMEM <= 160 * 1024, "LDS ring exceeds the CU's 160 KiB");
-  auto kern = gemm2_kernel<CF, TA, TB, OutT, EPI, SPLITK, NSTAGE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  dim3 grid(a.tiles_m * a.tiles_n, SPLITK ? split : 1);
-  hipLaunchKernelGGL(kern, grid, dim3(CF::NTH), SMEM, st, a);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+// ---- host side: ONE dispatch chain for the lockstep, ping-pong and persistent main loops ------------------------------------------------
+// Every refusal is decided by goat_tiles::gemm_row / grouped_row (gemm_tiles.hpp) before the chain is entered; the chain turns the accepted
+// run-time values into template constants and instantiates for a tile exactly what its table row lists.  A main loop is a policy L:
+// L::LOOP (its rows) and L::launch<CF, TA, TB, OutT, EPI, SPLITK, NSTAGE>, which names the kernel, its threads, LDS bytes and grid.
+using goat_tiles::Row;
+
+struct GemmCall {      // one accepted goat_gemm_bf16 launch
+  hipStream_t st;
+  const G2Args& a;
+  int trans_a, trans_b, dtype_out, epi, split, stages;
+};
+
+template <class L, class CF>
+constexpr Row row_of() { return *goat_tiles::find_row(L::LOOP, CF::BM, CF::BN, CF::EIGHT); }      // (no such row: not a constant expression)
+template <class CF>
+constexpr bool is_tile(const Row& r) { return r.bm == CF::BM && r.bn == CF::BN && r.eight == CF::EIGHT; }
+// every table row of unit u is one of CFs: asserted beside each unit's with_tile, whose arms they are (a row without an arm would be
+// accepted by the query and refused by the launch)
+template <class... CFs>
+constexpr bool unit_covered(goat_tiles::Unit u) {
+  for (const Row& r : goat_tiles::TABLE)
+    if (r.unit == u && !(is_tile<CFs>(r) || ...)) return false;
+  return true;
 }
 
-// ring depths a tile supports: whatever fits 160 KiB of LDS, 2..4
-template <class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK>
-int launch2(hipStream_t st, const G2Args& a, int split, int nstage) {
-  constexpr int STAGE = smem_bytes<CF, TA, TB, 1>();
-  if (nstage == 2) return launch2s<CF, TA, TB, OutT, EPI, SPLITK, 2>(st, a, split);
-  if constexpr (3 * STAGE <= 160 * 1024) {
-    if (nstage == 3) return launch2s<CF, TA, TB, OutT, EPI, SPLITK, 3>(st, a, split);
-  }
-  if constexpr (4 * STAGE <= 160 * 1024 && CF::BM * CF::BN <= 128 * 128) {
-    if (nstage == 4) return launch2s<CF, TA, TB, OutT, EPI, SPLITK, 4>(st, a, split);
-  }
+// run-time ring depth -> template constant, for the depths in MASK only: f(std::integral_constant<int, NSTAGE>)
+template <unsigned MASK, class F>
+int with_stages(int stages, F&& f) {
+  if constexpr ((MASK & goat_tiles::S2) != 0) if (stages == 2) return f(std::integral_constant<int, 2>());
+  if constexpr ((MASK & goat_tiles::S3) != 0) if (stages == 3) return f(std::integral_constant<int, 3>());
+  if constexpr ((MASK & goat_tiles::S4) != 0) if (stages == 4) return f(std::integral_constant<int, 4>());
   return GOAT_E_ARG;
 }
 
-// runtime epilogue id of a bf16 launch -> template constant: f(std::integral_constant<int, GOAT_EPI_...>) (host side)
+// runtime epilogue id of a bf16 launch -> template constant: f(std::integral_constant<int, GOAT_EPI_...>)
 template <class F>
 int with_epilogue(int epi, F&& f) {
   switch (epi) {
@@ -579,52 +594,59 @@ int with_epilogue(int epi, F&& f) {
   return GOAT_E_ARG;
 }
 
-template <class CF, bool TA, bool TB>
-int dispatch2(hipStream_t st, const G2Args& a, int dtype_out, int epi, int split, int nstage) {
-  if (split > 1) return launch2<CF, TA, TB, float, GOAT_EPI_NONE, true>(st, a, split, nstage);
-  if (dtype_out == GOAT_F32) {
-    if (epi != GOAT_EPI_NONE && epi != GOAT_EPI_ACCUM) return GOAT_E_ARG;
-    return launch2<CF, TA, TB, float, GOAT_EPI_NONE, false>(st, a, 1, nstage);
-  }
-  if constexpr (TA) {      // weight-gradient layout: bf16 results only without an epilogue (the activation epilogues belong to
-    if (epi != GOAT_EPI_NONE) return GOAT_E_ARG;      // forward / dgrad; not instantiating them saves a quarter of the build)
-    return launch2<CF, TA, TB, bf16_t, GOAT_EPI_NONE, false>(st, a, 1, nstage);
-  }
-  return with_epilogue(epi, [&](auto e) { return launch2<CF, TA, TB, bf16_t, decltype(e)::value, false>(st, a, 1, nstage); });
+template <class L, class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK>
+int launch_stages(const GemmCall& c) {
+  return with_stages<row_of<L, CF>().stages>(c.stages, [&](auto ns) {
+    return L::template launch<CF, TA, TB, OutT, EPI, SPLITK, decltype(ns)::value>(c.st, c.a, c.split);
+  });
 }
 
-// all operand layouts a tile supports (transposed operands need a power-of-two tile width on that side)
-template <class CF>
-int dispatch_layout(hipStream_t st, const G2Args& a, int trans_a, int trans_b, int dtype_out, int epi, int split, int nstage) {
-  constexpr bool POW2_M = (CF::BM & (CF::BM - 1)) == 0, POW2_N = (CF::BN & (CF::BN - 1)) == 0;
-  if (!trans_a && !trans_b) return dispatch2<CF, false, false>(st, a, dtype_out, epi, split, nstage);
-  if constexpr (POW2_N) {
-    if (!trans_a && trans_b) return dispatch2<CF, false, true>(st, a, dtype_out, epi, split, nstage);
-    if constexpr (POW2_M) {
-      if (trans_a && trans_b) return dispatch2<CF, true, true>(st, a, dtype_out, epi, split, nstage);
-    }
+// output type, split and epilogue.  (Float32 results carry no epilogue; GOAT_EPI_ACCUM is a flag of G2Args.  Transposed A: gemm_row let only
+// GOAT_EPI_NONE through.)
+template <class L, class CF, bool TA, bool TB>
+int dispatch2(const GemmCall& c) {
+  if constexpr (row_of<L, CF>().f32) {
+    if (c.split > 1) return launch_stages<L, CF, TA, TB, float, GOAT_EPI_NONE, true>(c);
+    if (c.dtype_out == GOAT_F32) return launch_stages<L, CF, TA, TB, float, GOAT_EPI_NONE, false>(c);
   }
+  if constexpr (TA && !L::DEAD_WGRAD_EPILOGUES) return launch_stages<L, CF, TA, TB, bf16_t, GOAT_EPI_NONE, false>(c);
+  else return with_epilogue(c.epi, [&](auto e) { return launch_stages<L, CF, TA, TB, bf16_t, decltype(e)::value, false>(c); });
+}
+
+// the operand layouts of the row
+template <class L, class CF>
+int dispatch_layout(const GemmCall& c) {
+  constexpr unsigned LAYOUTS = row_of<L, CF>().layouts;
+  if constexpr ((LAYOUTS & goat_tiles::NN) != 0) if (!c.trans_a && !c.trans_b) return dispatch2<L, CF, false, false>(c);
+  if constexpr ((LAYOUTS & goat_tiles::NT) != 0) if (!c.trans_a && c.trans_b) return dispatch2<L, CF, false, true>(c);
+  if constexpr ((LAYOUTS & goat_tiles::TT) != 0) if (c.trans_a && c.trans_b) return dispatch2<L, CF, true, true>(c);
   return GOAT_E_ARG;
 }
 
-template <class CF, int NSTAGE>
-int launch_group(hipStream_t st, const GroupArgs& g) {
-  constexpr int SMEM = smem_bytes<CF, true, true, NSTAGE>();
-  auto kern = gemm2_group_kernel<CF, NSTAGE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
+struct LockstepLoop {
+  static constexpr goat_tiles::Loop LOOP = goat_tiles::LOCKSTEP;
+  // The transposed-A tiles of this loop have always been compiled with the four activation epilogues too (56 kernels of gemm2.hip and
+  // gemm3.hip that no request reaches: the old dispatch lacked an `else`).  Kept, so that the device code stays as it was; false drops them.
+  static constexpr bool DEAD_WGRAD_EPILOGUES = true;
+  template <class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK, int NSTAGE>
+  static int launch(hipStream_t st, const G2Args& a, int split) {
+    constexpr int SMEM = smem_bytes<CF, TA, TB, NSTAGE>();
+    static_assert(SMEM <= 160 * 1024, "LDS ring exceeds the CU's 160 KiB: the table row lists a ring depth its tile cannot hold");
+    return launch_kernel<gemm2_kernel<CF, TA, TB, OutT, EPI, SPLITK, NSTAGE>>(dim3(a.tiles_m * a.tiles_n, SPLITK ? split : 1), dim3(CF::NTH), SMEM, st, a);
   }
-  hipLaunchKernelGGL(kern, dim3(g.tile_start[g.n]), dim3(CF::NTH), SMEM, st, g);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+};
+
+template <class CF>
+int launch_group(hipStream_t st, const GroupArgs& g, int stages) {
+  return with_stages<row_of<LockstepLoop, CF>().group_stages>(stages, [&](auto ns) {
+    constexpr int NSTAGE = decltype(ns)::value, SMEM = smem_bytes<CF, true, true, NSTAGE>();
+    static_assert(SMEM <= 160 * 1024, "LDS ring exceeds the CU's 160 KiB");
+    return launch_kernel<gemm2_group_kernel<CF, NSTAGE>>(dim3(g.tile_start[g.n]), dim3(CF::NTH), SMEM, st, g);
+  });
 }
 
 }  // namespace goat_g2
 
-// gemm3.hip: the 8-wave 192/256-wide tiles (tile = bm | bn << 16)
-int goat_g3_dispatch(hipStream_t st, const goat_g2::G2Args& a, int bm, int bn, int trans_a, int trans_b, int dtype_out, int epi,
-                     int split, int nstage);
-int goat_g3_group(hipStream_t st, const goat_g2::GroupArgs& g, int bm, int bn, int nstage);
+// gemm3.hip: the rows of unit GEMM3
+int goat_g3_gemm(const goat_g2::GemmCall& c, const goat_tiles::Row& row);
+int goat_g3_group(hipStream_t st, const goat_g2::GroupArgs& g, const goat_tiles::Row& row, int stages);

@@ -1,44 +1,43 @@
-// The ping-pong main loop (gemm5_tile.hpp) instantiated for its tile family; reached through goat_gemm_bf16 /
-// goat_wgrad_grouped with nstage | GOAT_GEMM_PP (nstage 2 = number of B buffers in LDS).
+// The ping-pong main loop (gemm5_tile.hpp) instantiated for its tile family, as itself and in its persistent form; reached through
+// goat_gemm_bf16 / goat_wgrad_grouped with nstage | GOAT_GEMM_PP (nstage 2 = number of B buffers in LDS).
 #include "gemm5_tile.hpp"
 
 using namespace goat_g5;
 
-int goat_g5_dispatch(hipStream_t st, const goat_g2::G2Args& a, int bm, int bn, int trans_a, int trans_b, int dtype_out, int epi,
-                     int split, int nstage, bool persist) {
-  if (persist) {
-    if (bm == 256 && bn == 256 && nstage == 2) return pp_dispatch_persist<P256x256>(st, a, trans_a, trans_b, dtype_out, epi, split);
-    if (bm == 192 && bn == 256 && nstage == 2) return pp_dispatch_persist<P192x256>(st, a, trans_a, trans_b, dtype_out, epi, split);
-    if (bm == 128 && bn == 256 && nstage == 2) return pp_dispatch_persist<P128x256>(st, a, trans_a, trans_b, dtype_out, epi, split);
-    if (bm == 256 && bn == 128 && nstage == 2) return pp_dispatch_persist<P256x128>(st, a, trans_a, trans_b, dtype_out, epi, split);
-    if (bm == 128 && bn == 128 && nstage == 2) return pp_dispatch_persist<P128x128>(st, a, trans_a, trans_b, dtype_out, epi, split);
+// tile of a PINGPONG / PERSISTENT row -> type: f(CF{})
+template <class F>
+static int with_tile(const Row& r, F&& f) {
+  if (is_tile<P256x256>(r)) return f(P256x256{});
+  if (is_tile<P192x256>(r)) return f(P192x256{});
+  if (is_tile<P128x256>(r)) return f(P128x256{});
+  if (is_tile<P256x128>(r)) return f(P256x128{});
+  if (is_tile<P128x128>(r)) return f(P128x128{});
+  return GOAT_E_ARG;
+}
+static_assert(unit_covered<P256x256, P192x256, P128x256, P256x128, P128x128>(goat_tiles::GEMM5), "a table row of this unit has no with_tile arm");
+
+int goat_g5_gemm(const GemmCall& c, const Row& row) {
+  if (row.loop == goat_tiles::PERSISTENT) return with_tile(row, [&](auto cf) { return dispatch_layout<PersistentLoop, decltype(cf)>(c); });
+  return with_tile(row, [&](auto cf) { return dispatch_layout<PingPongLoop, decltype(cf)>(c); });
+}
+
+int goat_g5_group(hipStream_t st, const GroupArgs& g, const Row& row) {
+  return with_tile(row, [&](auto cf) {
+    if constexpr (row_of<PingPongLoop, decltype(cf)>().group_stages != 0) return pp_launch_group<decltype(cf)>(st, g);
     return GOAT_E_ARG;
-  }
-  if (bm == 256 && bn == 256 && nstage == 2) return pp_dispatch_layout<P256x256>(st, a, trans_a, trans_b, dtype_out, epi, split);
-  if (bm == 192 && bn == 256 && nstage == 2) return pp_dispatch_layout<P192x256>(st, a, trans_a, trans_b, dtype_out, epi, split);
-  if (bm == 128 && bn == 256 && nstage == 2) return pp_dispatch_layout<P128x256>(st, a, trans_a, trans_b, dtype_out, epi, split);
-  if (bm == 256 && bn == 128 && nstage == 2) return pp_dispatch_layout<P256x128>(st, a, trans_a, trans_b, dtype_out, epi, split);
-  if (bm == 128 && bn == 128 && nstage == 2) return pp_dispatch_layout<P128x128>(st, a, trans_a, trans_b, dtype_out, epi, split);
-  return GOAT_E_ARG;
+  });
 }
 
-int goat_g5_group(hipStream_t st, const goat_g2::GroupArgs& g, int bm, int bn, int nstage) {
-  if (bm == 256 && bn == 256 && nstage == 2) return pp_launch_group<P256x256>(st, g);
-  if (bm == 128 && bn == 256 && nstage == 2) return pp_launch_group<P128x256>(st, g);
-  if (bm == 256 && bn == 128 && nstage == 2) return pp_launch_group<P256x128>(st, g);
-  return GOAT_E_ARG;
+int goat_g5_group_sk(hipStream_t st, const GroupArgs& g, const Row& row, void* ws, int64_t ws_bytes) {
+  return with_tile(row, [&](auto cf) {
+    if constexpr (row_of<PingPongLoop, decltype(cf)>().balanced) return pp_launch_group_sk<decltype(cf)>(st, g, ws, ws_bytes);
+    return GOAT_E_ARG;
+  });
 }
 
-int goat_g5_group_sk(hipStream_t st, const goat_g2::GroupArgs& g, int bm, int bn, int nstage, void* ws, int64_t ws_bytes) {
-  if (bm == 256 && bn == 256 && nstage == 2) return pp_launch_group_sk<P256x256>(st, g, ws, ws_bytes);
-  if (bm == 128 && bn == 256 && nstage == 2) return pp_launch_group_sk<P128x256>(st, g, ws, ws_bytes);
-  if (bm == 256 && bn == 128 && nstage == 2) return pp_launch_group_sk<P256x128>(st, g, ws, ws_bytes);
-  return GOAT_E_ARG;
-}
-
-int64_t goat_g5_group_sk_ws_bytes(int bm, int bn) {
-  if (bm == 256 && bn == 256) return pp_sk_ws_bytes<P256x256>();
-  if (bm == 128 && bn == 256) return pp_sk_ws_bytes<P128x256>();
-  if (bm == 256 && bn == 128) return pp_sk_ws_bytes<P256x128>();
-  return -1;
+int goat_g5_group_sk_ws_bytes(const Row& row) {
+  return with_tile(row, [&](auto cf) {
+    if constexpr (row_of<PingPongLoop, decltype(cf)>().balanced) return (int)pp_sk_ws_bytes<decltype(cf)>();
+    return -1;
+  });
 }

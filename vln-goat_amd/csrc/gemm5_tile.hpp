@@ -60,6 +60,7 @@ template <int MI_, int NI_, int NB_, int VAR_ = 0>
 struct PCfg {
   static constexpr int MI = MI_, NI = NI_, NB = NB_, VAR = VAR_;
   static constexpr int BM = 64 * MI, BN = 128 * NI, NTH = 512;
+  static constexpr bool EIGHT = false;     // (GOAT_GEMM_8WAVES names a lockstep tile; every tile here runs on eight waves)
   static constexpr int AH = MI * 4096;     // bytes of one A half-block (32*MI rows x 64 k)
   static constexpr int BSZ = NI * 16384;   // bytes of one B block (128*NI columns x 64 k)
   static constexpr int SMEM = 4 * AH + NB * BSZ;
@@ -196,79 +197,9 @@ __device__ __forceinline__ void sk_load_batch(const float* base, uint32_t voff, 
       : "memory");
 }
 
-// SK: 0 = a whole tile (every other launch form); segments of a contraction-balanced group: 1 = publish, 2 = finish, 3 = whole tile
-template <class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK, int SK = 0>
-__device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, const SkSeg* sk = nullptr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int MI = CF::MI, NI = CF::NI, NB = CF::NB, BM = CF::BM, BN = CF::BN, AH = CF::AH, BSZ = CF::BSZ;
-  static_assert(SK == 0 || (!SPLITK && sizeof(OutT) == 4 && TA), "segments: float32 weight-gradient tiles");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef Blk<TA, 32 * MI> BA;      // one A half-block
-  typedef Blk<TB, 128 * NI> BB;     // the B block
-  static_assert(BA::BYTES == AH && BB::BYTES == BSZ, "block sizes");
-  constexpr int PPW_A = BA::NP / 4, PPW_B = BB::NP / 4;     // pieces per wave: A half-block (group 1 issues two of them), B block (group 0)
-  static_assert(PPW_A * 4 == BA::NP && PPW_B * 4 == BB::NP, "pieces divide over the four waves of a group");
-  constexpr int WROWS = 32 * MI, WCOLS = 32 * NI;
-  constexpr bool SWAP = !SPLITK && sizeof(OutT) == 2;
-  constexpr uint32_t B_BASE = 4 * AH;
-
-  int tid_ = threadIdx.x;
-  if constexpr (SK != 0) asm volatile("" : "+v"(tid_));      // (called in a loop: keeps the lane-only address parts from being hoisted out of it and held in registers across the tiles)
-  const int tid = tid_, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = wave >> 2, wn = wave & 3;
-  const int hi = lane >> 5, l31 = lane & 31;
-
-  const int gsz = p.group_m * p.tiles_n;
-  const int grpi = bid / gsz, gi = bid - grpi * gsz;
-  const int gm = min(p.tiles_m - grpi * p.group_m, p.group_m);
-  const int tn = gi / gm, tm = grpi * p.group_m + (gi - tn * gm);
-  const int m0 = tm * BM, n0 = tn * BN;
-
-  int kt_begin = 0, kt_end = (p.Kc + BK - 1) / BK;
-  if (SPLITK) {
-    kt_begin = split * p.k_tiles_per_split;
-    kt_end = min(kt_end, kt_begin + p.k_tiles_per_split);
-    if (kt_begin >= kt_end) return;
-  }
-  if constexpr (SK != 0) { kt_begin = sk->kt_begin; kt_end = sk->kt_end; }
-  const int nkt = kt_end - kt_begin;
-
-  __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, (int)p.a_bytes, 0x00020000);
-  __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.B), 0, (int)p.b_bytes, 0x00020000);
-
-  // fragment read addresses (lane parts): A of this group's half-block, B of this wave's column patch
-  uint32_t va[4], vb[4];
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    va[x] = BA::frag_lane(lane, x) + (uint32_t)(grp * 2 * AH);
-    if (!TB) vb[x] = BB::frag_lane(lane, x) + (uint32_t)(wn * WCOLS * 128) + B_BASE;
-    else vb[x] = BB::frag_lane(lane, wn * NI + (x < NI ? x : 0)) + B_BASE;
-  }
-
-  AccTile<MI, NI> accs;
-  f32x16 (&acc)[MI][NI] = accs.t;
-#pragma unroll
-  for (int i = 0; i < MI; ++i)
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  bf16x8 fa[4][MI], fb[4][NI];
-
-  // bias gradient (column tile 0 only).  Whole tiles (SK == 0): the four waves of a group hold the same A fragments, so wave wn sums fragment row block
-  // i == wn — a quarter of the work each, every output row still has ONE writer (deterministic).  Segments of a contraction-balanced launch keep the
-  // one-wave form (their partial sums travel through the workspace in that layout).
-  constexpr bool BS_SPLIT = (SK == 0);
-  const bool do_colsum = TA && p.colsum != nullptr && tn == 0 && (BS_SPLIT ? wn < MI : wn == 0);
-  float bsum[MI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i) bsum[i] = 0.f;
-
-  const uint32_t smem_base = (uint32_t)(uintptr_t)(lds_void*)smem;
-  const uint32_t ka = TA ? (uint32_t)(BK * p.lda * 2) : (uint32_t)(BK * 2);     // source advance per K-tile
-  const uint32_t kb = TB ? (uint32_t)(BK * p.ldb * 2) : (uint32_t)(BK * 2);
-  const int k0 = kt_begin * BK;
-
+// ---- text shared by the two main loops below (pp_tile, pp_tiles_persist).  The macros expand inside those functions and use their locals:
+// fa fb va vb acc bsum, MI NI TA TB BA BB SWAP DPL BS_SPLIT do_colsum, wn smem ra rb vo pstep ka kb AH BSZ B_BASE PPW_A PPW_B, and the
+// per-site PP_STAMP / PP_ISSUE_RANGE.  The persistent loop is the DPL == 1, SWAP, no-colsum case.
   // all fragments of the K-tile in A buffer ab_ (byte offset inside this group's pair of buffers) and B buffer bb_
 #define PP_FRAGS_KS(KS, ao_, bo_)                                                                  \
   do {                                                                                             \
@@ -323,19 +254,6 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
     }                                                                                              \
   } while (0)
 
-  static_assert(NI <= 2 && MI <= 4, "fragment macros are written for MI <= 4, NI <= 2");
-
-  constexpr int DPL = CF::VAR & 3;            // LDS-DMA placement inside the MEM phase (see PCfg)
-#if GOAT_G5_TIMING
-  uint32_t tms[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) tms[i] = 0;
-  const uint32_t tm_start = g5_now();
-  uint32_t tm_c = tm_start;
-#define PP_STAMP(i_) do { const uint32_t n_ = g5_now(); tms[i_] += n_ - tm_c; tm_c = n_; } while (0)
-#else
-#define PP_STAMP(i_) do { } while (0)
-#endif
   // One slot pair of a group.  PP_ISSUE_RANGE(lo, hi) issues this wave's LDS-DMA pieces [lo, hi) of the period; LOADS of them.
 #define PP_PERIOD(LOADS_, ao_, bo_, WAITVM_, LASTBAR_)                                             \
   do {                                                                                             \
@@ -366,6 +284,107 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
     PP_STAMP(5);                                                                                   \
   } while (0)
 
+  // pieces [lo_, hi_) of this wave's share of B[t_] of the tile whose B origin is org_ -> B buffer buf_
+#define PP_ISSUE_B(org_, t_, buf_, lo_, hi_)                                                                   \
+  do {                                                                                                         \
+    char* dst_ = smem + B_BASE + (buf_) * BSZ + wn * PPW_B * 1024;                                             \
+    const uint32_t so_ = (org_) + (uint32_t)(t_) * kb;                                                         \
+    _Pragma("unroll") for (int j = (lo_); j < (hi_); ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(        \
+        rb, (lds_void*)(dst_ + j * 1024), 16, vo[j % BB::NPAR], so_ + (uint32_t)j * pstep, 0, 0);              \
+  } while (0)
+  // pieces [lo_, hi_) of this wave's share of the A half-block with origin org_ of K-tile t_ -> buffer buf_ of half h_
+#define PP_ISSUE_A(org_, h_, t_, buf_, lo_, hi_)                                                               \
+  do {                                                                                                         \
+    char* dst_ = smem + ((h_) * 2 + (buf_)) * AH + wn * PPW_A * 1024;                                          \
+    const uint32_t so_ = (org_) + (uint32_t)(t_) * ka;                                                         \
+    _Pragma("unroll") for (int j = (lo_); j < (hi_); ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(        \
+        ra, (lds_void*)(dst_ + j * 1024), 16, vo[j % BA::NPAR], so_ + (uint32_t)j * pstep, 0, 0);              \
+  } while (0)
+
+// SK: 0 = a whole tile (every other launch form); segments of a contraction-balanced group: 1 = publish, 2 = finish, 3 = whole tile
+template <class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK, int SK = 0>
+__device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, const SkSeg* sk = nullptr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int MI = CF::MI, NI = CF::NI, NB = CF::NB, BM = CF::BM, BN = CF::BN, AH = CF::AH, BSZ = CF::BSZ;
+  static_assert(SK == 0 || (!SPLITK && sizeof(OutT) == 4 && TA), "segments: float32 weight-gradient tiles");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  typedef Blk<TA, 32 * MI> BA;      // one A half-block
+  typedef Blk<TB, 128 * NI> BB;     // the B block
+  static_assert(BA::BYTES == AH && BB::BYTES == BSZ, "block sizes");
+  constexpr int PPW_A = BA::NP / 4, PPW_B = BB::NP / 4;     // pieces per wave: A half-block (group 1 issues two of them), B block (group 0)
+  static_assert(PPW_A * 4 == BA::NP && PPW_B * 4 == BB::NP, "pieces divide over the four waves of a group");
+  constexpr int WROWS = 32 * MI, WCOLS = 32 * NI;
+  constexpr bool SWAP = !SPLITK && sizeof(OutT) == 2;
+  constexpr uint32_t B_BASE = 4 * AH;
+
+  int tid_ = threadIdx.x;
+  if constexpr (SK != 0) asm volatile("" : "+v"(tid_));      // (called in a loop: keeps the lane-only address parts from being hoisted out of it and held in registers across the tiles)
+  const int tid = tid_, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int grp = wave >> 2, wn = wave & 3;
+  const int hi = lane >> 5, l31 = lane & 31;
+
+  int tm, tn;
+  tile_of_position(p, bid, tm, tn);
+  const int m0 = tm * BM, n0 = tn * BN;
+
+  int kt_begin = 0, kt_end = (p.Kc + BK - 1) / BK;
+  if (SPLITK) {
+    kt_begin = split * p.k_tiles_per_split;
+    kt_end = min(kt_end, kt_begin + p.k_tiles_per_split);
+    if (kt_begin >= kt_end) return;
+  }
+  if constexpr (SK != 0) { kt_begin = sk->kt_begin; kt_end = sk->kt_end; }
+  const int nkt = kt_end - kt_begin;
+
+  __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.A), 0, (int)p.a_bytes, 0x00020000);
+  __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.B), 0, (int)p.b_bytes, 0x00020000);
+
+  // fragment read addresses (lane parts): A of this group's half-block, B of this wave's column patch
+  uint32_t va[4], vb[4];
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    va[x] = BA::frag_lane(lane, x) + (uint32_t)(grp * 2 * AH);
+    if (!TB) vb[x] = BB::frag_lane(lane, x) + (uint32_t)(wn * WCOLS * 128) + B_BASE;
+    else vb[x] = BB::frag_lane(lane, wn * NI + (x < NI ? x : 0)) + B_BASE;
+  }
+
+  AccTile<MI, NI> accs;
+  f32x16 (&acc)[MI][NI] = accs.t;
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  bf16x8 fa[4][MI], fb[4][NI];
+
+  // bias gradient (column tile 0 only).  Whole tiles (SK == 0): the four waves of a group hold the same A fragments, so wave wn sums fragment row block
+  // i == wn — a quarter of the work each, every output row still has ONE writer (deterministic).  Segments of a contraction-balanced launch keep the
+  // one-wave form (their partial sums travel through the workspace in that layout).
+  constexpr bool BS_SPLIT = (SK == 0);
+  const bool do_colsum = TA && p.colsum != nullptr && tn == 0 && (BS_SPLIT ? wn < MI : wn == 0);
+  float bsum[MI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i) bsum[i] = 0.f;
+
+  const uint32_t smem_base = (uint32_t)(uintptr_t)(lds_void*)smem;
+  const uint32_t ka = TA ? (uint32_t)(BK * p.lda * 2) : (uint32_t)(BK * 2);     // source advance per K-tile
+  const uint32_t kb = TB ? (uint32_t)(BK * p.ldb * 2) : (uint32_t)(BK * 2);
+  const int k0 = kt_begin * BK;
+
+  static_assert(NI <= 2 && MI <= 4, "fragment macros are written for MI <= 4, NI <= 2");
+
+  constexpr int DPL = CF::VAR & 3;            // LDS-DMA placement inside the MEM phase (see PCfg)
+#if GOAT_G5_TIMING
+  uint32_t tms[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) tms[i] = 0;
+  const uint32_t tm_start = g5_now();
+  uint32_t tm_c = tm_start;
+#define PP_STAMP(i_) do { const uint32_t n_ = g5_now(); tms[i_] += n_ - tm_c; tm_c = n_; } while (0)
+#else
+#define PP_STAMP(i_) do { } while (0)
+#endif
   if (grp == 0) {
     // ---------------------------------------------------------------- group 0: loads B, computes rows [0, 32*MI)
     uint32_t vo[BB::NPAR];
@@ -374,16 +393,8 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
     for (int q = 0; q < BB::NPAR; ++q) vo[q] = BB::lane_off(lane, (q + par0) % BB::NPAR, p.ldb);
     const uint32_t org0 = BB::piece_org(wn * PPW_B, n0, k0, p.ldb);
     const uint32_t pstep = BB::piece_org(1, 0, 0, p.ldb);      // source distance between consecutive pieces
-    // pieces [lo_, hi_) of this wave's share of B[t_] -> B buffer buf_
-#define PP_ISSUE_B(t_, buf_, lo_, hi_)                                                                         \
-  do {                                                                                                         \
-    char* dst_ = smem + B_BASE + (buf_) * BSZ + wn * PPW_B * 1024;                                             \
-    const uint32_t so_ = org0 + (uint32_t)(t_) * kb;                                                           \
-    _Pragma("unroll") for (int j = (lo_); j < (hi_); ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(        \
-        rb, (lds_void*)(dst_ + j * 1024), 16, vo[j % BB::NPAR], so_ + (uint32_t)j * pstep, 0, 0);              \
-  } while (0)
-    PP_ISSUE_B(0, 0, 0, PPW_B);
-    if (NB == 3 && nkt > 1) PP_ISSUE_B(1, 1, 0, PPW_B);
+    PP_ISSUE_B(org0, 0, 0, 0, PPW_B);
+    if (NB == 3 && nkt > 1) PP_ISSUE_B(org0, 1, 1, 0, PPW_B);
     wait_vm<0>();
     __builtin_amdgcn_s_barrier();
 #if GOAT_G5_TIMING
@@ -397,8 +408,8 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
       // MEM phase in slot 2t (issues B[t+1], with three buffers B[t+2]), MFMA phase in slot 2t+1
 #define PP_ISSUE_RANGE(lo_, hi_)                                                                   \
   do {                                                                                             \
-    if (NB == 2) { if (t + 1 < nkt) PP_ISSUE_B(t + 1, nbuf, lo_, hi_); }                           \
-    else { if (t + 2 < nkt) PP_ISSUE_B(t + 2, n2, lo_, hi_); }                                     \
+    if (NB == 2) { if (t + 1 < nkt) PP_ISSUE_B(org0, t + 1, nbuf, lo_, hi_); }                           \
+    else { if (t + 2 < nkt) PP_ISSUE_B(org0, t + 2, n2, lo_, hi_); }                                     \
   } while (0)
 #define PP_WAITVM_G0                                                                               \
   do {                                                                                             \
@@ -410,7 +421,6 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
 #undef PP_WAITVM_G0
       bbuf = nbuf;
     }
-#undef PP_ISSUE_B
   } else {
     // ---------------------------------------------------------------- group 1: loads both A half-blocks, computes rows [32*MI, 64*MI)
     uint32_t vo[BA::NPAR];
@@ -420,17 +430,9 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
     const uint32_t org0 = BA::piece_org(wn * PPW_A, m0, k0, p.lda);
     const uint32_t org1 = BA::piece_org(wn * PPW_A, m0 + WROWS, k0, p.lda);
     const uint32_t pstep = BA::piece_org(1, 0, 0, p.lda);
-    // pieces [lo_, hi_) of this wave's share of half h_ (0/1) of K-tile t_ -> buffer buf_ of that half
-#define PP_ISSUE_A(h_, t_, buf_, lo_, hi_)                                                                     \
-  do {                                                                                                         \
-    char* dst_ = smem + ((h_) * 2 + (buf_)) * AH + wn * PPW_A * 1024;                                          \
-    const uint32_t so_ = ((h_) ? org1 : org0) + (uint32_t)(t_) * ka;                                           \
-    _Pragma("unroll") for (int j = (lo_); j < (hi_); ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(        \
-        ra, (lds_void*)(dst_ + j * 1024), 16, vo[j % BA::NPAR], so_ + (uint32_t)j * pstep, 0, 0);              \
-  } while (0)
-    PP_ISSUE_A(0, 0, 0, 0, PPW_A);
-    PP_ISSUE_A(1, 0, 0, 0, PPW_A);
-    if (nkt > 1) PP_ISSUE_A(0, 1, 1, 0, PPW_A);
+    PP_ISSUE_A(org0, 0, 0, 0, 0, PPW_A);
+    PP_ISSUE_A(org1, 1, 0, 0, 0, PPW_A);
+    if (nkt > 1) PP_ISSUE_A(org0, 0, 1, 1, 0, PPW_A);
     wait_vm<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_barrier();                   // slot 0: group 0 reads tile 0, nothing to compute here yet
@@ -443,14 +445,13 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
       // MEM phase in slot 2t+1: pieces [0, PPW_A) = A_1[t+1], [PPW_A, 2 PPW_A) = A_0[t+2]; MFMA phase in slot 2t+2
 #define PP_ISSUE_RANGE(lo_, hi_)                                                                   \
   do {                                                                                             \
-    if ((lo_) < PPW_A && t + 1 < nkt) PP_ISSUE_A(1, t + 1, (t + 1) & 1, (lo_), ((hi_) < PPW_A ? (hi_) : PPW_A)); \
-    if ((hi_) > PPW_A && t + 2 < nkt) PP_ISSUE_A(0, t + 2, t & 1, ((lo_) > PPW_A ? (lo_) - PPW_A : 0), (hi_) - PPW_A); \
+    if ((lo_) < PPW_A && t + 1 < nkt) PP_ISSUE_A(org1, 1, t + 1, (t + 1) & 1, (lo_), ((hi_) < PPW_A ? (hi_) : PPW_A)); \
+    if ((hi_) > PPW_A && t + 2 < nkt) PP_ISSUE_A(org0, 0, t + 2, t & 1, ((lo_) > PPW_A ? (lo_) - PPW_A : 0), (hi_) - PPW_A); \
   } while (0)
       PP_PERIOD(2 * PPW_A, ao, bo, wait_vm<0>(), (t + 1 < nkt));   // (group 0 has left its loop after its last MFMA phase)
 #undef PP_ISSUE_RANGE
       bbuf = bbuf + 1 == NB ? 0 : bbuf + 1;
     }
-#undef PP_ISSUE_A
   }
 #if GOAT_G5_TIMING
   if (p.aux != nullptr && lane == 0 && EPI == GOAT_EPI_NONE) {
@@ -461,11 +462,7 @@ __device__ __forceinline__ void pp_tile(const G2Args& p, int bid, int split, con
     o[7] = (uint32_t)nkt;
   }
 #endif
-#undef PP_PERIOD
 #undef PP_STAMP
-#undef PP_FRAGS_KS
-#undef PP_MMA_ALL
-#undef PP_BSUM
 
   // From here on the LDS ring is free: the last fragment reads of both groups completed before the barrier that ended the last
   // MEM phase, and no LDS-DMA is in flight.  Group 0 starts its epilogue while group 1 is in its last MFMA phase.
@@ -552,10 +549,7 @@ __global__ __launch_bounds__(512) void pp_kernel(G2Args p) {
 template <class CF>
 __global__ __launch_bounds__(512) void pp_group_kernel(GroupArgs g) {
   const int pos = xcd_chunk_position(blockIdx.x, gridDim.x);
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < GROUP_MAX; ++i)
-    if (i < g.n && pos >= g.tile_start[i]) pi = i;
+  const int pi = group_problem_of(g.tile_start, g.n, pos);
   const G2Args p = g.prob[pi].template expand<CF::BM, CF::BN>();
   pp_tile<CF, true, true, float, GOAT_EPI_NONE, false>(p, pos - g.tile_start[pi], 0);
 }
@@ -647,61 +641,21 @@ __global__ __launch_bounds__(512) void pp_group_sk_kernel(SkGroupArgs s) {
   }
 }
 
-template <class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK>
-int pp_launch(hipStream_t st, const G2Args& a, int split) {
-  static_assert(CF::SMEM <= 160 * 1024, "LDS exceeds the CU's 160 KiB");
-  auto kern = pp_kernel<CF, TA, TB, OutT, EPI, SPLITK>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
+// The loop as a policy of the dispatch chain (gemm2_tile.hpp: dispatch_layout).  NSTAGE = the NB of the product tiles.
+struct PingPongLoop {
+  static constexpr goat_tiles::Loop LOOP = goat_tiles::PINGPONG;
+  static constexpr bool DEAD_WGRAD_EPILOGUES = false;      // (see LockstepLoop)
+  template <class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK, int NSTAGE>
+  static int launch(hipStream_t st, const G2Args& a, int split) {
+    static_assert(CF::SMEM <= 160 * 1024 && NSTAGE == CF::NB, "LDS exceeds the CU's 160 KiB, or the table row lists a buffer count the tile does not have");
+    return launch_kernel<pp_kernel<CF, TA, TB, OutT, EPI, SPLITK>>(dim3(a.tiles_m * a.tiles_n, SPLITK ? split : 1), dim3(512), CF::SMEM, st, a);
   }
-  dim3 grid(a.tiles_m * a.tiles_n, SPLITK ? split : 1);
-  hipLaunchKernelGGL(kern, grid, dim3(512), CF::SMEM, st, a);
-  GOAT_LAUNCH_CHECK();
-  return 0;
-}
-
-template <class CF, bool TA, bool TB>
-int pp_dispatch2(hipStream_t st, const G2Args& a, int dtype_out, int epi, int split) {
-  if (split > 1) return pp_launch<CF, TA, TB, float, GOAT_EPI_NONE, true>(st, a, split);
-  if (dtype_out == GOAT_F32) {
-    if (epi != GOAT_EPI_NONE && epi != GOAT_EPI_ACCUM) return GOAT_E_ARG;
-    return pp_launch<CF, TA, TB, float, GOAT_EPI_NONE, false>(st, a, 1);
-  }
-  if constexpr (TA) {      // weight-gradient layout: bf16 results only without an epilogue
-    if (epi != GOAT_EPI_NONE) return GOAT_E_ARG;
-    return pp_launch<CF, TA, TB, bf16_t, GOAT_EPI_NONE, false>(st, a, 1);
-  } else {
-    return with_epilogue(epi, [&](auto e) { return pp_launch<CF, TA, TB, bf16_t, decltype(e)::value, false>(st, a, 1); });
-  }
-}
-
-template <class CF>
-int pp_dispatch_layout(hipStream_t st, const G2Args& a, int trans_a, int trans_b, int dtype_out, int epi, int split) {
-  if (!trans_a && !trans_b) return pp_dispatch2<CF, false, false>(st, a, dtype_out, epi, split);
-  if (!trans_a && trans_b) return pp_dispatch2<CF, false, true>(st, a, dtype_out, epi, split);
-  if constexpr ((CF::MI & (CF::MI - 1)) == 0) {      // a transposed A half-block needs a power-of-two width
-    if (trans_a && trans_b) return pp_dispatch2<CF, true, true>(st, a, dtype_out, epi, split);
-  }
-  return GOAT_E_ARG;
-}
+};
 
 template <class CF>
 int pp_launch_group(hipStream_t st, const GroupArgs& g) {
-  auto kern = pp_group_kernel<CF>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(g.tile_start[g.n]), dim3(512), CF::SMEM, st, g);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return launch_kernel<pp_group_kernel<CF>>(dim3(g.tile_start[g.n]), dim3(512), CF::SMEM, st, g);
 }
-
 
 // bytes of workspace a contraction-balanced group launch needs for tile CF on this device (slots + flags)
 template <class CF>
@@ -709,13 +663,6 @@ constexpr int pp_sk_slot_floats() { return 8 * CF::MI * CF::NI * 16 * 64 + 8 * C
 inline int pp_cu_count();
 template <class CF>
 int pp_launch_group_sk(hipStream_t st, const GroupArgs& g, void* ws, int64_t ws_bytes) {
-  auto kern = pp_group_sk_kernel<CF>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   static_assert(CF::SMEM > 80 * 1024, "one workgroup per CU (the wait relies on every workgroup being resident or ahead in dispatch order)");
   const int G = pp_cu_count();
   SkGroupArgs s;
@@ -732,9 +679,7 @@ int pp_launch_group_sk(hipStream_t st, const GroupArgs& g, void* ws, int64_t ws_
   if (ws == nullptr || (reinterpret_cast<uintptr_t>(ws) & 255) || ws_bytes < flag_off + (int64_t)G * 32) return GOAT_E_ARG;
   s.ws = reinterpret_cast<float*>(ws);
   s.flags = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(ws) + flag_off);
-  hipLaunchKernelGGL(kern, dim3(G), dim3(512), CF::SMEM, st, s);
-  GOAT_LAUNCH_CHECK();
-  return 0;
+  return launch_kernel<pp_group_sk_kernel<CF>>(dim3(G), dim3(512), CF::SMEM, st, s);
 }
 template <class CF>
 int64_t pp_sk_ws_bytes() {
@@ -794,47 +739,13 @@ __device__ __forceinline__ void pp_tiles_persist(const G2Args& p, int pos0, int 
   const uint32_t ka = (uint32_t)(BK * 2);
   const uint32_t kb = TB ? (uint32_t)(BK * p.ldb * 2) : (uint32_t)(BK * 2);
 
-#define PP_FRAGS_KS(KS, ao_, bo_)                                                                  \
-  do {                                                                                             \
-    fa[KS][0] = pp_frag<TA, BA::W, KS, 0>(va, ao_);                                                \
-    if constexpr (MI > 1) fa[KS][1 < MI ? 1 : 0] = pp_frag<TA, BA::W, KS, 1>(va, ao_);             \
-    if constexpr (MI > 2) fa[KS][2 < MI ? 2 : 0] = pp_frag<TA, BA::W, KS, 2>(va, ao_);             \
-    if constexpr (MI > 3) fa[KS][3 < MI ? 3 : 0] = pp_frag<TA, BA::W, KS, 3>(va, ao_);             \
-    fb[KS][0] = pp_frag<TB, BB::W, KS, 0>(vb, bo_);                                                \
-    if constexpr (NI > 1) fb[KS][1 < NI ? 1 : 0] = pp_frag<TB, BB::W, KS, 1>(vb, bo_);             \
-  } while (0)
-#define PP_MMA_ALL()                                                                               \
-  do {                                                                                             \
-    if (GOAT_G5_SETPRIO) __builtin_amdgcn_s_setprio(1);                                            \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                               \
-      _Pragma("unroll") for (int i = 0; i < MI; ++i)                                               \
-        _Pragma("unroll") for (int j = 0; j < NI; ++j) mma32(acc[i][j], fb[ks][j], fa[ks][i]);     \
-    if (GOAT_G5_SETPRIO) __builtin_amdgcn_s_setprio(0);                                            \
-  } while (0)
   static_assert(NI <= 2 && MI <= 4, "fragment macros are written for MI <= 4, NI <= 2");
   static_assert((CF::VAR & 3) == 1, "the persistent form uses DMA placement 1");
-#define PP_PERIOD(LOADS_, ao_, bo_, WAITVM_, LASTBAR_)                                             \
-  do {                                                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                                             \
-    PP_FRAGS_KS(0, ao_, bo_);                                                                      \
-    { __builtin_amdgcn_sched_barrier(0); PP_ISSUE_RANGE(0, LOADS_ / 4); __builtin_amdgcn_sched_barrier(0); } \
-    PP_FRAGS_KS(1, ao_, bo_);                                                                      \
-    { __builtin_amdgcn_sched_barrier(0); PP_ISSUE_RANGE(LOADS_ / 4, LOADS_ / 2); __builtin_amdgcn_sched_barrier(0); } \
-    PP_FRAGS_KS(2, ao_, bo_);                                                                      \
-    { __builtin_amdgcn_sched_barrier(0); PP_ISSUE_RANGE(LOADS_ / 2, 3 * LOADS_ / 4); __builtin_amdgcn_sched_barrier(0); } \
-    PP_FRAGS_KS(3, ao_, bo_);                                                                      \
-    { __builtin_amdgcn_sched_barrier(0); PP_ISSUE_RANGE(3 * LOADS_ / 4, LOADS_); __builtin_amdgcn_sched_barrier(0); } \
-    wait_lgkm<0>();                                                                                \
-    __builtin_amdgcn_s_barrier();                                                                  \
-    __builtin_amdgcn_sched_barrier(0);                                                             \
-    PP_MMA_ALL();                                                                                  \
-    __builtin_amdgcn_sched_barrier(0);                                                             \
-    WAITVM_;                                                                                       \
-    if (LASTBAR_) __builtin_amdgcn_s_barrier();                                                    \
-    __builtin_amdgcn_sched_barrier(0);                                                             \
-  } while (0)
-
-  // tile position -> (first row, first column), pp_tile's order
+  constexpr int DPL = 1;
+  constexpr bool BS_SPLIT = true;      // (no bias gradient here: do_colsum is false)
+#define PP_STAMP(i_) do { } while (0)
+  // tile position -> (first row, first column), pp_tile's order: goat_g2::tile_of_position written out with gsz hoisted out of the tile loop (through
+  // the helper the twenty K-contiguous-B kernels schedule 4 to 14 instructions differently: profiles/gemm_dispatch_fold_isa_diff.txt)
   const int gsz = p.group_m * p.tiles_n;
 #define PP_COORDS(pos_, m0_, n0_)                                                                  \
   do {                                                                                             \
@@ -858,23 +769,6 @@ __device__ __forceinline__ void pp_tiles_persist(const G2Args& p, int pos0, int 
     for (int q = 0; q < BA::NPAR; ++q) vo[q] = BA::lane_off(lane, (q + par0) % BA::NPAR, p.lda);
     pstep = BA::piece_org(1, 0, 0, p.lda);
   }
-  // pieces [lo_, hi_) of this wave's share of B[t_] of the tile whose B origin is org_ -> B buffer buf_
-#define PP_ISSUE_B(org_, t_, buf_, lo_, hi_)                                                                   \
-  do {                                                                                                         \
-    char* dst_ = smem + B_BASE + (buf_) * BSZ + wn * PPW_B * 1024;                                             \
-    const uint32_t so_ = (org_) + (uint32_t)(t_) * kb;                                                         \
-    _Pragma("unroll") for (int j = (lo_); j < (hi_); ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(        \
-        rb, (lds_void*)(dst_ + j * 1024), 16, vo[j % BB::NPAR], so_ + (uint32_t)j * pstep, 0, 0);              \
-  } while (0)
-  // pieces [lo_, hi_) of this wave's share of the A half-block with origin org_ of K-tile t_ -> buffer buf_ of half h_
-#define PP_ISSUE_A(org_, h_, t_, buf_, lo_, hi_)                                                               \
-  do {                                                                                                         \
-    char* dst_ = smem + ((h_) * 2 + (buf_)) * AH + wn * PPW_A * 1024;                                          \
-    const uint32_t so_ = (org_) + (uint32_t)(t_) * ka;                                                         \
-    _Pragma("unroll") for (int j = (lo_); j < (hi_); ++j) __builtin_amdgcn_raw_ptr_buffer_load_lds(        \
-        ra, (lds_void*)(dst_ + j * 1024), 16, vo[j % BA::NPAR], so_ + (uint32_t)j * pstep, 0, 0);              \
-  } while (0)
-
   int m0, n0;
   PP_COORDS(pos0, m0, n0);
   // the first tile's first K-tile (pp_tile's prologue)
@@ -955,14 +849,17 @@ __device__ __forceinline__ void pp_tiles_persist(const G2Args& p, int pos0, int 
     m0 = nm0;
     n0 = nn0;
   }
+#undef PP_COORDS
+#undef PP_STAMP
+#endif  // __HIP_DEVICE_COMPILE__
+}
+
 #undef PP_ISSUE_A
 #undef PP_ISSUE_B
-#undef PP_COORDS
 #undef PP_PERIOD
 #undef PP_FRAGS_KS
 #undef PP_MMA_ALL
-#endif  // __HIP_DEVICE_COMPILE__
-}
+#undef PP_BSUM
 
 template <class CF, bool TB, int EPI>
 __global__ __launch_bounds__(512) void pp_persist_kernel(G2Args p) {
@@ -984,35 +881,23 @@ inline int pp_cu_count() {
   return n;
 }
 
-template <class CF, bool TB, int EPI>
-int pp_launch_persist(hipStream_t st, const G2Args& a) {
-  static_assert(CF::SMEM <= 160 * 1024, "LDS exceeds the CU's 160 KiB");
-  auto kern = pp_persist_kernel<CF, TB, EPI>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, CF::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
+// The persistent loop as a policy of the dispatch chain: its rows of the table have bf16 results, unsplit, K-contiguous A.
+struct PersistentLoop {
+  static constexpr goat_tiles::Loop LOOP = goat_tiles::PERSISTENT;
+  static constexpr bool DEAD_WGRAD_EPILOGUES = false;      // (see LockstepLoop)
+  template <class CF, bool TA, bool TB, typename OutT, int EPI, bool SPLITK, int NSTAGE>
+  static int launch(hipStream_t st, const G2Args& a, int) {
+    static_assert(!TA && !SPLITK && sizeof(OutT) == 2 && NSTAGE == CF::NB, "pp_tiles_persist: bf16 results, unsplit, K-contiguous A");
+    static_assert(CF::SMEM <= 160 * 1024, "LDS exceeds the CU's 160 KiB");
+    const int nt = a.tiles_m * a.tiles_n, slots = pp_cu_count() * (CF::SMEM <= 80 * 1024 ? 2 : 1);
+    return launch_kernel<pp_persist_kernel<CF, TB, EPI>>(dim3(nt < slots ? nt : slots), dim3(512), CF::SMEM, st, a);
   }
-  const int nt = a.tiles_m * a.tiles_n, slots = pp_cu_count() * (CF::SMEM <= 80 * 1024 ? 2 : 1);
-  hipLaunchKernelGGL(kern, dim3(nt < slots ? nt : slots), dim3(512), CF::SMEM, st, a);
-  GOAT_LAUNCH_CHECK();
-  return 0;
-}
-
-// persistent launches: bf16 results, unsplit, K-contiguous A; anything else -> GOAT_E_ARG
-template <class CF>
-int pp_dispatch_persist(hipStream_t st, const G2Args& a, int trans_a, int trans_b, int dtype_out, int epi, int split) {
-  if (trans_a || split > 1 || dtype_out != GOAT_BF16) return GOAT_E_ARG;
-  if (!trans_b) return with_epilogue(epi, [&](auto e) { return pp_launch_persist<CF, false, decltype(e)::value>(st, a); });
-  return with_epilogue(epi, [&](auto e) { return pp_launch_persist<CF, true, decltype(e)::value>(st, a); });
-}
+};
 
 }  // namespace goat_g5
 
-// gemm5.hip
-int goat_g5_dispatch(hipStream_t st, const goat_g2::G2Args& a, int bm, int bn, int trans_a, int trans_b, int dtype_out, int epi,
-                     int split, int nstage, bool persist);
-int goat_g5_group(hipStream_t st, const goat_g2::GroupArgs& g, int bm, int bn, int nstage);
-int goat_g5_group_sk(hipStream_t st, const goat_g2::GroupArgs& g, int bm, int bn, int nstage, void* ws, int64_t ws_bytes);
-int64_t goat_g5_group_sk_ws_bytes(int bm, int bn);
+// gemm5.hip: the rows of unit GEMM5
+int goat_g5_gemm(const goat_g2::GemmCall& c, const goat_tiles::Row& row);
+int goat_g5_group(hipStream_t st, const goat_g2::GroupArgs& g, const goat_tiles::Row& row);
+int goat_g5_group_sk(hipStream_t st, const goat_g2::GroupArgs& g, const goat_tiles::Row& row, void* ws, int64_t ws_bytes);
+int goat_g5_group_sk_ws_bytes(const goat_tiles::Row& row);       // 256 slots of <= 264 KiB: fits an int

@@ -60,7 +60,7 @@ __global__ void probe_tr16_kernel(uint16_t* out) {
 
 }  // namespace
 
-extern "C" int goat_version(void) { return 106; }
+extern "C" int goat_version(void) { return 107; }
 
 extern "C" int goat_probe_tr16(void* stream, uint16_t* out) {
   if (!out) return GOAT_E_ARG;

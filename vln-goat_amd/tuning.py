@@ -10,6 +10,7 @@ import os
 
 import torch
 
+from . import _lib
 from ._lib import EPI_NONE
 from ._plumbing import _dt, call, cargs
 
@@ -54,10 +55,13 @@ def save_tuned(path):
 
 
 
-EIGHT_WAVES = 0x100     # GOAT_GEMM_8WAVES (include/goat_hip.h): flag in the nstage argument of goat_gemm_bf16
-PINGPONG = 0x200        # GOAT_GEMM_PP: the ping-pong main loop (csrc/gemm5_tile.hpp); tiles 256x256, 192x256, 128x256, 256x128, 128x128
-BALANCED = 0x800        # (grouped weight gradients only) goat_wgrad_grouped_balanced: one workgroup per CU, equal shares of the group's K-tile iterations
-PERSIST = 0x400         # GOAT_GEMM_PERSIST (with PINGPONG): one workgroup per CU walks the tiles, next tile's first K-tile requested before the epilogue
+# Flags in the nstage argument of goat_gemm_bf16 / goat_wgrad_grouped.  Defined HERE for Python, once; the first three are include/goat_hip.h's
+# GOAT_GEMM_8WAVES / GOAT_GEMM_PP / GOAT_GEMM_PERSIST (tests/test_gemm_dispatch_table.py reads the header and compares).
+EIGHT_WAVES = 0x100     # the 128 x 128 tile on eight waves
+PINGPONG = 0x200        # the ping-pong main loop (csrc/gemm5_tile.hpp)
+PERSIST = 0x400         # (with PINGPONG) one workgroup per CU walks the tiles, next tile's first K-tile requested before the epilogue
+BALANCED = 0x800        # Python only, never passed to C: WgradQueue._run routes such a configuration to goat_wgrad_grouped_balanced (one workgroup
+                        # per CU, equal shares of the group's K-tile iterations) and passes the tile alone
 USE_PP = os.environ.get('GOAT_GEMM_NO_PP', '0') == '0'
 USE_PERSIST = os.environ.get('GOAT_GEMM_NO_PERSIST', '0') == '0'
 N_CU = 256              # MI355X; `n_cu()` reads the device (decides which shapes get the persistent candidates timed, and the tail split of a group)
@@ -119,6 +123,18 @@ def _tile_candidates(ta, tb, M, N):
     return c
 
 
+def gemm_in_build(ta, tb, out_dtype, epi, split_k, bm, nstage):
+    """does this build of the library have the goat_gemm_bf16 configuration?  (the lookup the entry point itself performs; nothing is launched)"""
+    return _lib.lib().goat_gemm_bf16_query(int(ta), int(tb), _lib.GOAT_F32 if out_dtype == torch.float32 else _lib.GOAT_BF16, epi, split_k, bm, nstage) == 0
+
+
+def grouped_in_build(bm, nstage):
+    """... the grouped weight-gradient configuration (tile, ring stages | flags), BALANCED included?"""
+    if nstage & BALANCED:
+        return nstage == BALANCED | PINGPONG | 2 and _lib.lib().goat_wgrad_balanced_ws_bytes(bm) > 0
+    return _lib.lib().goat_wgrad_grouped_query(bm, nstage) == 0
+
+
 def _heuristic_cfg(ta, tb, M, N, Kc, split_k):
     """(bm, nstage) measured with scripts/gemm_bench.py (hot and cold operands)."""
     tiles128 = ((M + 127) // 128) * ((N + 127) // 128) * max(1, split_k)
@@ -173,10 +189,9 @@ def _tune_gemm(key, a, b, out, ta, tb, M, N, Kc, bias, epi, aux, split_opts, col
         for bm, ns in _tile_candidates(ta, tb, M, N):
             if bm == 128 and (ns & 0xFF) == 4 and out.dtype == torch.bfloat16 and epi != EPI_NONE:
                 continue
-            try:
-                t = _time_cfg(lambda: _launch_gemm_bf16(a, b, scratch, ta, tb, M, N, Kc, bias, epi, aux, split, bm, ns, cs))
-            except RuntimeError:
+            if not gemm_in_build(ta, tb, out.dtype, epi, split, bm, ns):
                 continue
+            t = _time_cfg(lambda: _launch_gemm_bf16(a, b, scratch, ta, tb, M, N, Kc, bias, epi, aux, split, bm, ns, cs))       # (a launch that fails here raises)
             if split > 1:       # a split launch needs its float32 output cleared first: count that fill (ms)
                 t += 1.5e-3 + out.numel() * 4 / 4.0e9
             if best is None or t < best[0]:

@@ -20,14 +20,14 @@ class WgradQueue:
     The first write of a slice in a step overwrites it; a later write (shared weights, BPTT) is queued as an accumulation —
     never in the same group as an earlier write of that slice (hipops._sink flushes first)."""
     enabled = os.environ.get('GOAT_WGRAD_GROUP', '1') != '0'
-    # (tile = rows | cols << 16, ring stages | 0x100 = eight waves on 128x128 | 0x200 = ping-pong): scripts/wgrad_group_bench.py.  The configuration of a
+    # (tuning.tile(rows, cols), ring stages | tuning.EIGHT_WAVES / PINGPONG): scripts/wgrad_group_bench.py.  The configuration of a
     # group the tuner has not timed — above all the groups of a CAPTURED step when its eager warm-up ran on one stream: a capture forks parallel
     # branches, each stream has its own queue, so the groups differ from the warm-up's and miss the tuned plans (found in round 5: 10 of the 12
     # groups of the headline cycle ran this default, then 256 x 128 on three ring slots; the 256 x 256 ping-pong tile wins nearly every group the
     # tuner times: step 5.30 -> 5.18 ms same box, profiles/round5_wgrad_default_cfg_ab.txt).  Branch.like_capture() makes a warm-up form the capture's groups.
     cfg = tuple(int(v) for v in os.environ['GOAT_WGRAD_GROUP_CFG'].split(',')) if 'GOAT_WGRAD_GROUP_CFG' in os.environ else (
         tuple(int(v) for v in os.environ['GOAT_WGRAD_DEFAULT_CFG'].split(',')) if 'GOAT_WGRAD_DEFAULT_CFG' in os.environ else (   # (A/B: default without switching the tuner off)
-            (256 | 256 << 16, 0x200 | 2) if USE_PP else (256, 3)))
+            (tile(256, 256), PINGPONG | 2) if USE_PP else (256, 3)))
     MAX = int(os.environ.get('GOAT_WGRAD_GROUP_MAX', '48'))      # problems per launch = the kernel's GROUP_MAX (48 since the last session of round 5: 24 / 32 / 48 -> 5.03 / 5.02 / 4.99 ms per step; round 1: 8 / 12 / 16 -> 7.12 / 7.09 /
                                                                  # 7.06 ms per step; round 4, same box, three alternations: 16 -> 5.80 / 5.81 / 5.80, 24 -> 5.75 / 5.76 / 5.76)
     # (round 2 also had a mode that ran the grouped launches on a stream of their own, off the dgrad chain: 6.52 vs 6.28 ms per step — the
@@ -224,10 +224,16 @@ class WgradQueue:
             return None
         return best
 
+    @staticmethod
+    def _balanced_fits(q, t):
+        """goat_wgrad_grouped_balanced refuses (GOAT_E_SHAPE) a group with fewer K-tile iterations than the device has CUs: nothing to balance"""
+        rows, cols = t & 0xFFFF, (t >> 16) or 128
+        return sum(-(-p[0].shape[1] // rows) * -(-p[1].shape[1] // cols) * -(-p[0].shape[0] // 64) for p in q) >= n_cu()
+
     @classmethod
     def _plans(cls, q):
         n = len(q)
-        plans = [[(tuple(range(n)), c)] for c in cls.CANDIDATES]
+        plans = [[(tuple(range(n)), c)] for c in cls.CANDIDATES if not c[1] & BALANCED or cls._balanced_fits(q, c[0])]
         tail = cls._tail_split(q)
         if tail is not None:
             head = tuple(i for i in range(n) if i not in tail)
@@ -271,6 +277,8 @@ class WgradQueue:
         scratch = [torch.empty((t[0].shape[1], t[1].shape[1]), dtype=torch.float32, device=t[0].device) for t in q]
         best = None
         for cand in cls._plans(q):
+            if not all(tuning.grouped_in_build(*cfg) for _, cfg in cand):      # (asked, not tried: a launch that fails below raises)
+                continue
             parts = []
             for idx, cfg in cand:
                 arr = (_lib.WgradProblem * len(idx))()
@@ -280,10 +288,7 @@ class WgradQueue:
             def run():
                 for arr, m, cfg in parts:
                     _lib.check(cls._run(arr, m, cfg, tuning=True), 'goat_wgrad_grouped (tuning)')
-            try:
-                t = _time_cfg(run, reps=int(os.environ.get('GOAT_WGRAD_TUNE_REPS', '9')))      # (a group runs 0.1-0.5 ms: nine repetitions cost nothing and the picks stop flipping between runs)
-            except RuntimeError:
-                continue
+            t = _time_cfg(run, reps=int(os.environ.get('GOAT_WGRAD_TUNE_REPS', '9')))      # (a group runs 0.1-0.5 ms: nine repetitions cost nothing and the picks stop flipping between runs)
             if os.environ.get('GOAT_WGRAD_PLAN_LOG'):
                 import sys
                 print('[wgrad group] %d problems rows %s: %s -> %.1f us' % (n, sorted({t_[0].shape[0] for t_ in q}), ' + '.join(
